@@ -5,7 +5,13 @@ synthetic (long key, long ts, long val) records, 1M uniform keys, batches of 2^2
 runs it: 5 warm-up + 20 timed = 1.34e9 timed records), bounded out-of-orderness D = 1 s,
 wm = max_ts - D - 1 after every batch, final wm = Long.MAX.
 A step = one batch pushed through the engine + the watermark advance that fires its windows. Inputs are
-generated into HBM before timing; outputs stay in HBM.
+generated into HBM before timing; outputs stay in HBM. The input buffers hold up to 96 GiB (64
+batches by default); a run of more steps is timed in segments of that many steps, and the buffers are refilled with the
+next part of the same stream between the segments, outside the timing, so --steps is not bounded by the HBM size.
+
+A plain run sets up, warms up, times the steps and prints the result line. `--full` adds the secondary legs of the C2
+line (cpu_baseline, pcie_inclusive, wide_keys, wire_input; each has its own --no-* switch). `--dump-outputs DIR`
+writes the rows the last timed step fired (the final watermark's flush) as DIR/<column>.npy, see dump_outputs().
 
 N>1 (torchrun, one rank per GPU): weak scaling -- every rank sources a stream of the same size and
 event-time range (its own key/value seeds), records are routed to their key-group owner with RCCL
@@ -23,6 +29,7 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
+INPUT_BYTES = 96 << 30      # input buffers in HBM: 64 batches of 2^26 records of 24 B
 HBM_PEAK_GBPS = 8000.0   # MI355X HBM3E spec (MI355X_MICROARCH.md chip table)
 C2_RECORDS = 1_000_000_000
 C2_SPAN_MS = 1_000_000   # 1000 s of event time for 1e9 records
@@ -41,6 +48,17 @@ def main():
     ap.add_argument("--keys", type=int, default=1_000_000)
     ap.add_argument("--window-ms", type=int, default=10_000)
     ap.add_argument("--delay-ms", type=int, default=1000)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary legs of the C2 line after the timed steps: the CPU baseline, the "
+                         "PCIe-inclusive, 64-bit-key and wire-input legs (off by default: a plain run only sets up, "
+                         "warms up, times the steps and prints the result line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the rows the last timed step fired as DIR/<column>.npy "
+                         "(float32/float64, rows in (win_end, win_start, key) order; a seeded row sample when the "
+                         "columns exceed 64 MB)")
+    ap.add_argument("--chunk-steps", type=int, default=0,
+                    help="batches the input buffers hold (default: what fits in 96 GiB, 64 at the default batch); runs "
+                         "of more steps regenerate the buffers between timed segments, outside the timing")
     ap.add_argument("--cpu-sample", type=int, default=6 << 26)
     ap.add_argument("--cpu-threads", type=int, default=0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -112,24 +130,43 @@ def main():
         w = 1.0 / np.arange(1, args.keys + 1, dtype=np.float64) ** 1.1
         zcdf = torch.from_numpy(np.cumsum(w) / w.sum()).to(dev)
         p.zipf_cdf = zcdf.data_ptr()
-    log("rank %d/%d generating %d records (%.1f GB) in HBM" % (rank, world, n_rank, n_rank * 24 / 1e9))
-    keys = torch.empty(n_rank, dtype=torch.int64, device=dev)
+    # The input buffers hold `chunk` batches. A run of more steps than that goes through the stream chunk by chunk:
+    # the next chunk is generated into the same buffers between two timed segments, outside the timing (the
+    # generator is counter-based, so the stream is the one a single buffer of S batches would hold).
+    chunk = min(S, args.chunk_steps or max(1, INPUT_BYTES // ((28 if fp else 24) * B)))
+    log("rank %d/%d: %d records (%.1f GB) in %d batches, generated in HBM %d batches (%.1f GB) at a time"
+        % (rank, world, n_rank, n_rank * 24 / 1e9, S, chunk, chunk * B * 24 / 1e9))
+    keys = torch.empty(chunk * B, dtype=torch.int64, device=dev)
     ts = torch.empty_like(keys)
     if fp:
-        vals = torch.empty(n_rank, dtype=torch.float32, device=dev)
-        vals_d = torch.empty(n_rank, dtype=torch.float64, device=dev)
-        E.generate(p, n_rank, keys, ts, None, vals, vals_d, device=local_rank)
+        vals = torch.empty(chunk * B, dtype=torch.float32, device=dev)
+        vals_d = torch.empty(chunk * B, dtype=torch.float64, device=dev)
     else:
         vals = torch.empty_like(keys)
-        E.generate(p, n_rank, keys, ts, vals, device=local_rank)
-    torch.cuda.synchronize()
-    bmax = ts.view(S, B).max(dim=1).values.cpu().numpy()
-    wms = []
-    m = -2**63
-    for b in range(S):
-        m = max(m, int(bmax[b]))
-        wms.append(m - args.delay_ms - 1)          # BoundedOutOfOrdernessWatermarks.onPeriodicEmit
-    wms[-1] = A.LONG_MAX                           # final watermark flushes every window
+    wms = [None] * S     # the watermark after batch b, filled in as the chunks are generated
+    wm_state = {"max_ts": -2**63, "gen_s": 0.0}
+
+    def load(lo):
+        """Generate batches [lo, lo + chunk) of the stream into the buffers (slot b - lo); returns the end."""
+        t0 = time.perf_counter()
+        hi = min(S, lo + chunk)
+        p.first_index = lo * B
+        if fp:
+            E.generate(p, (hi - lo) * B, keys, ts, None, vals, vals_d, device=local_rank)
+        else:
+            E.generate(p, (hi - lo) * B, keys, ts, vals, device=local_rank)
+        torch.cuda.synchronize()
+        if wms[hi - 1] is None:
+            bmax = ts[:(hi - lo) * B].view(hi - lo, B).max(dim=1).values.cpu().numpy()
+            for b in range(lo, hi):
+                wm_state["max_ts"] = max(wm_state["max_ts"], int(bmax[b - lo]))
+                wms[b] = wm_state["max_ts"] - args.delay_ms - 1   # BoundedOutOfOrdernessWatermarks.onPeriodicEmit
+            if hi == S:
+                wms[-1] = A.LONG_MAX                           # final watermark flushes every window
+        wm_state["gen_s"] += time.perf_counter() - t0
+        return hi
+    base = 0             # first batch of the chunk in the buffers
+    chunk_end = load(0)
 
     win_kw = dict(window_kind="TUMBLE", semantics="DATASTREAM", size_ms=args.window_ms)
     if args.config == "c3":
@@ -147,10 +184,17 @@ def main():
     cfg_kw = dict(**win_kw,
                   aggs=aggs, key_capacity=int(args.keys * float(os.environ.get("FWA_KCAP", "1"))),
                   output_on_device=1, device=local_rank, reduce=args.config == "reduce")
-    cols_of = (lambda b: [vals[b * B:(b + 1) * B], vals_d[b * B:(b + 1) * B]]) if fp else \
-        (lambda b: [vals[b * B:(b + 1) * B], ts[b * B:(b + 1) * B]]) if args.config == "reduce" else \
-        (lambda b: [vals[b * B:(b + 1) * B]])
+    # slot j of the buffers holds batch base + j
+    cols_of = (lambda j: [vals[j * B:(j + 1) * B], vals_d[j * B:(j + 1) * B]]) if fp else \
+        (lambda j: [vals[j * B:(j + 1) * B], ts[j * B:(j + 1) * B]]) if args.config == "reduce" else \
+        (lambda j: [vals[j * B:(j + 1) * B]])
+    views = [(keys[j * B:(j + 1) * B], ts[j * B:(j + 1) * B], cols_of(j)) for j in range(chunk)]
     pipelined = None
+    last = []    # the rows of the latest watermark step (engine-owned device columns, valid until the next call)
+
+    def keep(res):
+        last[:] = [res]
+        return res
     if args.exchange == "auto":
         from flink_amd.distributed import choose_exchange
         args.exchange = "raw" if args.config == "reduce" else choose_exchange(cfg_kw)   # reductions: no partials
@@ -160,70 +204,85 @@ def main():
         pipe = cls(rank, world, **cfg_kw)
         eng = pipe.local if args.exchange == "partials" else pipe.engine   # the ingest path being measured
         engines = [pipe.engine] + ([pipe.local] if args.exchange == "partials" else [])
-        batch_of = lambda b: (keys[b * B:(b + 1) * B], ts[b * B:(b + 1) * B], cols_of(b))  # noqa: E731
-        push = lambda b: pipe.push(*batch_of(b))  # noqa: E731
-        fire = lambda b: pipe.advance_watermark(wms[b], device_output=True)["key"].shape[0]  # noqa: E731
+        push = lambda b: pipe.push(*views[b - base])  # noqa: E731
+        fire = lambda b: keep(pipe.advance_watermark(wms[b], device_output=True))["key"].shape[0]  # noqa: E731
         if args.exchange == "partials":
             # software pipelining across steps: batch b+1 enters the local pre-aggregator while batch b's partials
             # are exchanged, merged and fired (same per-engine call order; every timed batch is pushed and fired
             # inside the timed region)
-            pipelined = lambda b, nxt: pipe.advance_watermark(  # noqa: E731
-                wms[b], device_output=True, then_push=batch_of(nxt) if nxt is not None else None)["key"].shape[0]
+            pipelined = lambda b, nxt: keep(pipe.advance_watermark(  # noqa: E731
+                wms[b], device_output=True, then_push=views[nxt - base] if nxt is not None else None))["key"].shape[0]
     else:
         eng = E.WindowAggregator(A.make_config(**cfg_kw))
-        views = [(keys[b * B:(b + 1) * B], ts[b * B:(b + 1) * B], cols_of(b)) for b in range(S)]
-        push = lambda b: eng.push(*views[b], sync=False)  # noqa: E731
+        push = lambda b: eng.push(*views[b - base], sync=False)  # noqa: E731
         # fired rows stay in HBM (engine-owned device columns); only the row count comes back
-        fire = lambda b: eng.advance_watermark_raw(wms[b]).n_rows  # noqa: E731
+        fire = lambda b: keep(eng.advance_watermark_raw(wms[b])).n_rows  # noqa: E731
         engines = [eng]
 
-    rows = 0
     async_fire = world == 1 and not args.sync_fire
-    for b in range(args.warmup):
-        push(b)
-        if async_fire:        # the same calls as the timed loop (output buffers grown, modes settled before timing)
-            if b > 0:
-                rows += eng.fired_output_raw().n_rows
-            eng.advance_watermark_async(wms[b])
+
+    def run(lo, hi, t_before=None):
+        """Steps [lo, hi) of the chunk in the buffers; t_before: timed steps (seconds timed so far, for the log) --
+        warm-up steps make the same calls (output buffers grown, modes settled before timing). Returns (rows fired,
+        records dropped as late)."""
+        timed = t_before is not None
+        t0 = time.perf_counter()
+        rows = drop = 0
+
+        def progress(b):
+            if timed and (b - args.warmup) % 4 == 3 and (args.steps <= 100 or (b - args.warmup) % 100 == 99):
+                log("step %d/%d  %.2fs" % (b - args.warmup + 1, args.steps, t_before + time.perf_counter() - t0))
+        if timed and pipelined is not None:
+            push(lo)
+            for b in range(lo, hi):
+                rows += pipelined(b, b + 1 if b + 1 < hi else None)
+                progress(b)
+        elif async_fire:
+            # the watermark step returns while its fire runs (fwa_advance_watermark_async); the fired rows are taken
+            # after the next batch was handed over, so the host's work for batch b+1 overlaps the fire of batch b
+            for b in range(lo, hi):
+                drop += push(b)
+                if b > lo:
+                    rows += eng.fired_output_raw().n_rows
+                eng.advance_watermark_async(wms[b])
+                progress(b)
+            rows += keep(eng.fired_output_raw()).n_rows
         else:
-            rows += fire(b)
-    if async_fire and args.warmup > 0:
-        rows += eng.fired_output_raw().n_rows
-    for x in engines:
-        x.reset_timers()
-    if world > 1:
-        dist.barrier()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
+            for b in range(lo, hi):
+                drop += push(b)
+                rows += fire(b)
+                progress(b)
+        return rows, drop
+
     rows_t = 0
     dropped = 0
-    if pipelined is not None:
-        push(args.warmup)
-        for b in range(args.warmup, S):
-            rows_t += pipelined(b, b + 1 if b + 1 < S else None)
-            if (b - args.warmup) % 4 == 3:
-                log("step %d/%d  %.2fs" % (b - args.warmup + 1, args.steps, time.perf_counter() - t0))
-    elif async_fire:
-        # the watermark step returns while its fire runs (fwa_advance_watermark_async); the fired rows are taken
-        # after the next batch was handed over, so the host's work for batch b+1 overlaps the fire of batch b
-        for b in range(args.warmup, S):
-            dropped += push(b)
-            if b > args.warmup:
-                rows_t += eng.fired_output_raw().n_rows
-            eng.advance_watermark_async(wms[b])
-            if (b - args.warmup) % 4 == 3:
-                log("step %d/%d  %.2fs" % (b - args.warmup + 1, args.steps, time.perf_counter() - t0))
-        rows_t += eng.fired_output_raw().n_rows
-    else:
-        for b in range(args.warmup, S):
-            dropped += push(b)
-            rows_t += fire(b)
-            if (b - args.warmup) % 4 == 3:
-                log("step %d/%d  %.2fs" % (b - args.warmup + 1, args.steps, time.perf_counter() - t0))
-    torch.cuda.synchronize()
-    if world > 1:
-        dist.barrier()
-    elapsed = time.perf_counter() - t0
+    elapsed = 0.0
+    while True:
+        if base < args.warmup:
+            run(base, min(chunk_end, args.warmup))
+        if chunk_end > args.warmup:
+            if base <= args.warmup:
+                for x in engines:
+                    x.reset_timers()
+            if world > 1:
+                dist.barrier()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            r, d = run(max(base, args.warmup), chunk_end, elapsed)
+            torch.cuda.synchronize()
+            if world > 1:
+                dist.barrier()
+            elapsed += time.perf_counter() - t0
+            rows_t += r
+            dropped += d
+        if chunk_end == S:
+            break
+        torch.cuda.synchronize()    # every read of the buffers has finished before the next chunk overwrites them
+        base = chunk_end
+        chunk_end = load(base)
+    if S > chunk:
+        log("inputs generated in %d chunks, %.2f s outside the timed segments" % ((S + chunk - 1) // chunk,
+                                                                                 wm_state["gen_s"]))
     if world > 1:
         rdev = dev if backend == "nccl" else "cpu"
         t = torch.tensor([elapsed], dtype=torch.float64, device=rdev)
@@ -234,6 +293,8 @@ def main():
         rows_all = int(rr.item())
     else:
         rows_all = rows_t
+    if args.dump_outputs is not None:    # before any further call on the engine: its output columns are still valid
+        dump_outputs(args.dump_outputs, last[0] if world > 1 else device_rows(eng, last[0]), rank, world)
     st = eng.stats()
     recs_timed = args.steps * B * world
     value = recs_timed / elapsed
@@ -342,18 +403,65 @@ def main():
         "late_dropped": sum(x.stats().late_dropped for x in engines) if args.exchange == "partials" or world == 1 else dropped,
     }
     out["roofline"]["replay_records"] = st.replay_records
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.config == "c2":
+    legs = args.full and rank == 0 and world == 1 and args.config == "c2"   # the secondary legs of the C2 line
+    args.leg_batches = chunk
+    if legs and S > chunk:   # the legs take the first batches of the stream
+        base = 0
+        load(0)
+    if legs and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args, cfg_kw)
-    if rank == 0 and world == 1 and not args.no_pcie and args.config == "c2":
+    if legs and not args.no_pcie:
         out["pcie_inclusive"] = pcie_leg(args, cfg_kw, keys, ts, vals, wms, dev)
-    if rank == 0 and world == 1 and not args.no_wide and args.config == "c2":
+    if legs and not args.no_wide:
         out["wide_keys"] = wide_keys_leg(args, cfg_kw, keys, ts, vals, wms, dev)
-    if rank == 0 and world == 1 and not args.no_wire and args.config == "c2":
+    if legs and not args.no_wire:
         out["wire_input"] = wire_leg(args, cfg_kw, keys, ts, vals, wms, dev)
     if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()
+
+
+DUMP_MAX_BYTES = 64_000_000   # --dump-outputs: all files together
+DUMP_SAMPLE_SEED = 0x5eed0d0
+
+
+def device_rows(eng, out):
+    """Torch views of the engine-owned device columns of one watermark step (WindowAggregator.advance_watermark_device
+    for an `Out` that was already taken)."""
+    from flink_amd import _abi as A
+    from flink_amd import engine as E
+    n = out.n_rows
+    res = {f: E.dev_view(getattr(out, f), n, np.dtype("i8")) for f in ("key", "win_start", "win_end")}
+    for j, name in enumerate(eng.names):
+        res["agg%d" % j] = E.dev_view(out.agg[j], n, np.dtype(A.AGG_RESULT_DTYPE[name]))
+    return res
+
+
+def dump_outputs(path, rows, rank, world):
+    """--dump-outputs: the rows the last timed step fired, one DIR/<column>.npy per output column (key, win_start,
+    win_end, agg<j>; `.rank<r>` before the suffix at N>1), float32 for FLOAT columns and float64 for the others (the
+    workloads' int64 values stay below 2^53). The engine emits rows in no fixed order, so they are written sorted by
+    (win_end, win_start, key), which is unique per row. Columns of more than DUMP_MAX_BYTES together (over all ranks)
+    are cut to a row sample drawn from the sorted rows with a fixed seed; n_rows.npy holds the row count before
+    sampling. The integer workloads (C2, C3, C4, reduce) repeat bit for bit from run to run; the SUM / AVG(double)
+    columns of C5 and C5s repeat to the last bit or two (the engine's order of floating-point additions is not
+    fixed), every other column exactly."""
+    os.makedirs(path, exist_ok=True)
+    n = int(rows["key"].shape[0])
+    order = torch.argsort(rows["key"], stable=True)
+    for f in ("win_start", "win_end"):
+        order = order[torch.argsort(rows[f][order], stable=True)]
+    m = DUMP_MAX_BYTES // world // (8 * len(rows)) - 64   # per rank; room for the .npy headers and n_rows.npy
+    if n > m:
+        pick = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=m, replace=False))
+        order = order[torch.from_numpy(pick).to(order.device)]
+    suffix = ".rank%d.npy" % rank if world > 1 else ".npy"
+    for name, col in rows.items():
+        a = col[order].cpu().numpy()
+        np.save(os.path.join(path, name + suffix), a.astype(np.float32 if a.dtype == np.float32 else np.float64))
+    np.save(os.path.join(path, "n_rows" + suffix), np.array([n], dtype=np.float64))
+    log("wrote %d of %d rows (%d columns) to %s" % (min(n, m), n, len(rows), path))
 
 
 def ingest_kernels(args, eng):
@@ -434,7 +542,7 @@ def pcie_leg(args, cfg_kw, keys, ts, vals, wms, dev):
     from flink_amd import _abi as A
     from flink_amd import engine as E
     B = args.batch
-    nb = min(args.pcie_batches, args.warmup + args.steps)
+    nb = min(args.pcie_batches, args.leg_batches)
     hk = torch.empty(nb * B, dtype=torch.int64, pin_memory=True)
     ht = torch.empty_like(hk, pin_memory=True)
     hv = torch.empty_like(hk, pin_memory=True)
@@ -468,7 +576,7 @@ def wide_keys_leg(args, cfg_kw, keys, ts, vals, wms, dev):
     from flink_amd import _abi as A
     from flink_amd import engine as E
     B = args.batch
-    nb = min(args.wide_batches, args.warmup + args.steps)
+    nb = min(args.wide_batches, args.leg_batches)
     wk = keys[:nb * B] + (1 << 40)
     eng = E.WindowAggregator(A.make_config(**cfg_kw))
     views = [(wk[b * B:(b + 1) * B], ts[b * B:(b + 1) * B], [vals[b * B:(b + 1) * B]]) for b in range(nb)]
@@ -525,7 +633,7 @@ def wire_leg(args, cfg_kw, keys, ts, vals, wms, dev):
     from flink_amd import engine as E
     from flink_amd import wire
     B = args.batch
-    nb = min(args.wire_batches, args.warmup + args.steps)
+    nb = min(args.wire_batches, args.leg_batches)
     bufs = [encode_c2_wire(keys[b * B:(b + 1) * B], ts[b * B:(b + 1) * B], vals[b * B:(b + 1) * B], wms[b], dev)
             for b in range(nb)]
     torch.cuda.synchronize()

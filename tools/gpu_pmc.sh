@@ -4,7 +4,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 R=$PWD
 mkdir -p gpurun_out/pmc
 cd /tmp && export TMPDIR=/tmp
-ARGS=${PMC_ARGS:---steps 2 --warmup 1 --no-cpu-baseline}
+ARGS=${PMC_ARGS:---full --steps 2 --warmup 1 --no-cpu-baseline}
 i=0
 IFS=';' read -ra PASSES <<< "${PASSES:-FETCH_SIZE;WRITE_SIZE;SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS;TCC_HIT_sum TCC_MISS_sum GRBM_GUI_ACTIVE}"
 for pass in "${PASSES[@]}"; do

@@ -3,8 +3,8 @@
     python tools/roofline_from_trace.py <run_kernel_trace.csv> <bench json line file> [--out profiles/x.json]
 
 The trace is `rocprofv3 --kernel-trace --output-format csv -- python3 bench.py --gpus 1 --steps K --warmup W ...`.
-The main engine's calls come first in bench.py (W warm-up steps, then K timed steps; the PCIe and wire legs
-create their own engines afterwards), so the timed dispatches of a kernel family are its occurrences
+The main engine's calls come first in bench.py (W warm-up steps, then K timed steps; with --full the PCIe and wire
+legs create their own engines afterwards), so the timed dispatches of a kernel family are its occurrences
 [W, W + K) in dispatch order, counted on the main engine's HIP stream (the stream of the first ingest
 dispatch). Only steady-state timed dispatches enter the average: cold dispatches of the warm-up steps and
 the side legs are excluded.
