@@ -316,6 +316,156 @@ __global__ void __launch_bounds__(kBlock) fire_kernel(FireArgs f, const EngineCo
     }
 }
 
+// TUMBLE fire of up to kWalkMaxWin one-slot windows in one pass per kid chunk (fire_kernel<1> and fire_multi_kernel
+// re-read the key table once per window: a watermark firing W windows moved W x 8 B per kid for it). One block owns
+// kBlock * 2V consecutive kids (a thread: V pairs, 16-byte loads), loads their keys and presence once and walks the
+// windows; window w + 1's accumulator loads are issued before window w's rows are stored (the stores may alias them as
+// far as the compiler knows). One row reservation per (block, window), rows j-major as fire_kernel.
+// A window with retire != 0 leaves this watermark for good (retire_slices would release its slot next): the identities
+// (0; MIN columns 0xFF..) are stored right behind the loads, 16 B per lane over the whole chunk, and block 0 clears the
+// slot's touched flag, so the host releases the slot without reset_slots_kernel's second dense pass. The host sets
+// retire only when every row fits out_cap (no count-and-relaunch). check_st: the fire was enqueued behind a push whose
+// status the host has not seen; spill_n / late_fire / error are final in stream order, and when one is set the host
+// discards this fire and fires again after the replay -- the kernel then emits and clears nothing.
+// The window table travels in the kernel arguments: no upload.
+constexpr int kWalkMaxWin = 8;
+struct WalkWin {
+    int64_t start, end;
+    unsigned long long* base;   // the window's slot
+    int32_t slot, retire;
+};
+struct WalkArgs {
+    const unsigned long long* key_table;
+    int64_t capacity, stride;
+    int64_t* o_key;
+    int64_t* o_start;
+    int64_t* o_end;
+    void* o_agg[FWA_MAX_AGGS];
+    uint8_t* o_null[FWA_MAX_AGGS];
+    int64_t out_cap;
+    DevStatus* st;
+    int32_t* touched;
+    int32_t nwin, check_st;
+    WalkWin win[kWalkMaxWin];
+};
+
+// (uniform column base + a 32-bit lane offset: one offset register per pair serves every column of every window)
+template <int NA, int V>
+__device__ __forceinline__ void walk_load(ulonglong2 (&x)[NA][V], const unsigned long long* base, int64_t stride, int64_t k0,
+                                          uint32_t rem, int tid) {
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+        const uint32_t r = (uint32_t)(v * kBlock + tid) * 2u;     // stride % 64 == 0: the pair is inside or outside
+#pragma unroll
+        for (int a = 0; a < NA; ++a) {
+            const char* col = (const char*)(base + (int64_t)a * stride + k0);
+            x[a][v] = r < rem ? *(const ulonglong2*)(col + (size_t)(r * 8u)) : make_ulonglong2(0ull, 0ull);
+        }
+    }
+}
+
+template <int NA, int V>
+__global__ void __launch_bounds__(kBlock) fire_walk_kernel(WalkArgs f, const EngineConst* __restrict__ cp) {
+    const EngineConst& c = *cp;
+    if (f.check_st && (f.st->spill_n != 0 || f.st->late_fire != 0 || f.st->error != 0)) return;
+    constexpr int S = 2 * V;                       // ballots per window
+    constexpr int kWaves = kBlock / 64;
+    static_assert(S * kWaves <= 64, "one wave scans the block's counts");
+    const int64_t nk = f.capacity + 1;
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    __shared__ uint32_t woff[2][S * kWaves];       // double-buffered by window parity: two barriers per window
+    __shared__ unsigned long long s_base[2];
+    const int64_t k0 = (int64_t)blockIdx.x * kBlock * S;
+    // the block's kids as 32-bit offsets r from k0: r < rem inside the columns, < remk inside the key table, < capr an
+    // ordinary key slot, == capr the side slot
+    const uint32_t rem = (uint32_t)min(f.stride - k0, (int64_t)kBlock * S);
+    const uint32_t remk = (uint32_t)max((int64_t)0, min(nk - k0, (int64_t)kBlock * S));
+    const uint32_t capr = (uint32_t)max((int64_t)0, min(f.capacity - k0, (int64_t)1 << 30));
+    if (blockIdx.x == 0 && tid < f.nwin && f.win[tid].retire) f.touched[f.win[tid].slot] = 0;
+    ulonglong2 kv[V];
+    uint32_t pres = 0;                             // bit 2v + h: kid h of pair v holds a key
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+        const uint32_t r = (uint32_t)(v * kBlock + tid) * 2u;
+        const char* kb = (const char*)(f.key_table + k0);
+        if (r + 1 < remk) kv[v] = *(const ulonglong2*)(kb + (size_t)(r * 8u));
+        else kv[v] = make_ulonglong2(r < remk ? *(const unsigned long long*)(kb + (size_t)(r * 8u)) : kEmptyKey, kEmptyKey);
+        const bool p0 = r < capr ? kv[v].x != kEmptyKey : (r == capr && kv[v].x == 1ull);
+        const bool p1 = r + 1 < capr ? kv[v].y != kEmptyKey : (r + 1 == capr && kv[v].y == 1ull);
+        pres |= (p0 ? 1u : 0u) << (2 * v) | (p1 ? 2u : 0u) << (2 * v);
+    }
+    ulonglong2 cur[NA][V], nxt[NA][V];
+    walk_load<NA, V>(cur, f.win[0].base, f.stride, k0, rem, tid);
+    const unsigned long long lt = (1ull << lane) - 1ull;
+    for (int w = 0; w < f.nwin; ++w) {
+        const WalkWin win = f.win[w];
+        if (w + 1 < f.nwin) walk_load<NA, V>(nxt, f.win[w + 1].base, f.stride, k0, rem, tid);
+        if (win.retire) {
+#pragma unroll
+            for (int a = 0; a < NA; ++a) {
+                const unsigned long long id = (a > 0 && c.acc_kind[a] == ACC_MIN_ORD) ? ~0ull : 0ull;
+                char* col = (char*)(win.base + (int64_t)a * f.stride + k0);
+#pragma unroll
+                for (int v = 0; v < V; ++v) {
+                    const uint32_t r = (uint32_t)(v * kBlock + tid) * 2u;
+                    if (r < rem) *(ulonglong2*)(col + (size_t)(r * 8u)) = make_ulonglong2(id, id);
+                }
+            }
+        }
+        uint32_t* wo = woff[w & 1];
+        unsigned long long masks[S];
+#pragma unroll
+        for (int s = 0; s < S; ++s) {
+            const unsigned long long cnt = (s & 1) ? cur[0][s >> 1].y : cur[0][s >> 1].x;
+            masks[s] = __ballot(((pres >> s) & 1u) && cnt != 0);
+            if (lane == 0) wo[s * kWaves + wid] = (uint32_t)__popcll(masks[s]);
+        }
+        __syncthreads();
+        if (wid == 0) {                            // exclusive scan of the S * kWaves counts, one reservation
+            const uint32_t t = lane < S * kWaves ? wo[lane] : 0u;
+            uint32_t incl = t;
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) {
+                const uint32_t y = __shfl_up(incl, d);
+                if (lane >= d) incl += y;
+            }
+            if (lane < S * kWaves) wo[lane] = incl - t;
+            if (lane == 63) s_base[w & 1] = incl ? atomicAdd(&f.st->rows, (unsigned long long)incl) : 0ull;
+        }
+        __syncthreads();
+        const int64_t base_row = (int64_t)s_base[w & 1];
+#pragma unroll
+        for (int s = 0; s < S; ++s) {
+            if (!((masks[s] >> lane) & 1ull)) continue;
+            const int64_t row = base_row + wo[s * kWaves + wid] + __popcll(masks[s] & lt);
+            if (row >= f.out_cap) continue;
+            const uint32_t r = (uint32_t)((s >> 1) * kBlock + tid) * 2u + (s & 1);
+            const unsigned long long kk = (s & 1) ? kv[s >> 1].y : kv[s >> 1].x;
+            f.o_key[row] = (r < capr) ? (int64_t)kk : LONG_MIN_J;
+            f.o_start[row] = win.start;
+            f.o_end[row] = win.end;
+            const unsigned long long cnt = (s & 1) ? cur[0][s >> 1].y : cur[0][s >> 1].x;
+            for (int a = 0; a < c.nout; ++a) {
+                const AggDesc d = c.agg[a];
+                unsigned long long xv = ident_of(d.acc_kind), nn = 0;
+#pragma unroll
+                for (int q = 1; q < NA; ++q) {     // register selects, no dynamic index
+                    const unsigned long long xq = (s & 1) ? cur[q][s >> 1].y : cur[q][s >> 1].x;
+                    if (q == d.acc) xv = xq;
+                    if (q == d.nn) nn = xq;
+                }
+                write_agg(d, cnt, xv, nn, f.o_agg[a], f.o_null[a], row);
+            }
+        }
+        if (w + 1 < f.nwin) {
+#pragma unroll
+            for (int a = 0; a < NA; ++a)
+#pragma unroll
+                for (int v = 0; v < V; ++v) cur[a][v] = nxt[a][v];
+        }
+    }
+}
+
 // drain_route (fwa_drain_route): the raw fire of complete slices (fwa_drain_partials) written straight into the
 // exchange's send layout -- packed partial rows grouped by owning subtask (KeyGroupStreamPartitioner.selectChannel,
 // KeyGroupStreamPartitioner.java:55-65) -- so the drain and the keyBy routing are one pass over the slot columns. One
@@ -1860,12 +2010,36 @@ __global__ void __launch_bounds__(64) late_fire_kernel(LateArgs L, const EngineC
     *L.rows = nrow;
 }
 
+// The push's slice tables (rel2slot | relcode | relfresh, push_v2) for live slices spanning at most kRelTabN relative
+// slices, by value: push_reset_kernel expands them into the device tables partition3 / combine3 read (an upload from
+// the host left the GPU idle for ~18 us in front of every push). Outside [lo, lo + n): no slot, kCodeSlow, not fresh,
+// what the uploaded tables hold there.
+constexpr int kRelTabN = 32;
+struct RelTab {
+    int32_t lo, n;
+    int32_t slot[kRelTabN];
+    uint8_t code[kRelTabN], fresh[kRelTabN];
+};
+
 // two-phase path, the bucket cursors: one launch instead of a string of memsets.
-__global__ void push_reset_kernel(DevStatus* st, unsigned long long* want, int32_t nwant, uint32_t* bcnt, int32_t nbcnt) {
+__global__ void push_reset_kernel(DevStatus* st, unsigned long long* want, int32_t nwant, uint32_t* bcnt, int32_t nbcnt,
+                                  int32_t* rel2slot, RelTab tab) {
     const int32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     const int32_t nt = gridDim.x * blockDim.x;
+    if (rel2slot) {
+        uint8_t* code = (uint8_t*)(rel2slot + kRelCap);
+        uint8_t* fresh = code + kRelCap;
+        for (int32_t i = t; i < kRelCap; i += nt) {
+            const int32_t j = i - tab.lo;
+            const bool in = j >= 0 && j < tab.n;
+            rel2slot[i] = in ? tab.slot[j] : -1;
+            code[i] = in ? tab.code[j] : kCodeSlow;
+            fresh[i] = in ? tab.fresh[j] : (uint8_t)0;
+        }
+    }
     if (t == 0) {
         st->error = 0; st->spill_n = 0; st->want_n = 0; st->key_full = 0;
+        st->rows = 0;   // the next fire's row counter (fwa_engine::rows_zero): no memset in front of it
         st->dropped = 0; st->late_fire = 0; st->max_q = 0; st->min_q = ~0ull; st->ovf_n = 0; st->strag_n = 0; st->wide_n = 0;
     }
     for (int32_t i = t; i < nwant; i += nt) want[i] = 0ull;
@@ -2155,6 +2329,9 @@ struct fwa_engine {
     // per-handle options (fwa_set_option; the defaults are the production behaviour)
     int32_t opt_pre = -1, opt_mp = -1, opt_narrow = -1, opt_cells = -1;   // -1 adaptive, 0 never, 1 always
     int32_t opt_variant = 0;                                              // FWA_OPT_INGEST_VARIANT (A/B builds)
+    bool rows_zero = false;             // d_st->rows is 0: push_reset_kernel ran and nothing has fired since
+    int64_t fused_fires = 0;            // fires that also retired their slots (FWA_OPT_FUSED_FIRES)
+    int64_t reset_launches = 0;         // reset_slots_kernel launches (FWA_OPT_RESET_LAUNCHES)
     int32_t push_epoch = 0;             // epoch of the current / last push (touched flags hold the last one per slot)
     // fire_slide's carried window sums: valid for a run whose first window starts at slice rs_q0 while the slices
     // [rs_q0, rs_q0 + rs_u0) have not been touched by a push after epoch rs_epoch
@@ -2471,6 +2648,7 @@ int flush_resets(fwa_engine* e) {
     reset_slots_kernel<<<dim3((unsigned)blocks, (unsigned)n), 256, 0, e->stream>>>(e->d_slot_base, e->d_reset_list, inl,
                                                                                   e->stride, e->d_touched, e->d_ec);
     HIPCHK(e, hipGetLastError());
+    e->reset_launches++;
     e->pending_reset.clear();
     return FWA_OK;
 }
@@ -2617,11 +2795,15 @@ int upload(fwa_engine* e, void* dst, const void* src, size_t bytes) {
     return FWA_OK;
 }
 
-int reset_push_status(fwa_engine* e, bool v2bufs = false) {
-    // zero everything but n_keys / rows; min_q starts at ~0; want-set; v2: bucket cursors
+int reset_push_status(fwa_engine* e, bool v2bufs = false, const RelTab* tab = nullptr) {
+    // zero everything but n_keys; min_q starts at ~0; want-set; v2: bucket cursors, and the slice tables given by value
+    RelTab none;
+    memset(&none, 0, sizeof(none));
     push_reset_kernel<<<64, kBlock, 0, e->stream>>>(e->d_st, e->d_want, e->d_want ? kWantCap : 0,
-                                                    v2bufs ? e->d_bcnt : nullptr, v2bufs ? kMaxPart * kSub : 0);
+                                                    v2bufs ? e->d_bcnt : nullptr, v2bufs ? kMaxPart * kSub : 0,
+                                                    tab ? e->d_rel2slot : nullptr, tab ? *tab : none);
     HIPCHK(e, hipGetLastError());
+    e->rows_zero = true;
     return FWA_OK;
 }
 
@@ -3172,9 +3354,11 @@ static int push_v2(fwa_engine* e, IngestArgs& a, bool* ran) {
     // slots no record reached yet hold their identities: the combiner's merge of such a slice stores without reading
     uint8_t* fresh = code + kRelCap;
     memset(fresh, 0, kRelCap);
+    int64_t rel_hi = -1;                              // (rel_lo = 0: q_base is the first live slice)
     for (auto& kv : e->live) {
         const int64_t rel = kv.first - q_base;
         if (rel < 0 || rel >= kRelCap) continue;
+        rel_hi = rel;
         r2s[rel] = kv.second;
         fresh[rel] = (e->touched[kv.second] || (e->opt_variant & 1)) ? 0 : 1;   // variant bit 0: A/B without
         int64_t thr;
@@ -3184,9 +3368,17 @@ static int push_v2(fwa_engine* e, IngestArgs& a, bool* ran) {
         else if (e->lateness > 0 && a.wm >= trig(e, jm::wsub(first_window_end(e, kv.first), 1))) code[rel] = kCodeSlow;
         else code[rel] = kCodeAccept;
     }
-    rc = upload(e, e->d_rel2slot, r2s.data(), (sizeof(int32_t) + 2) * kRelCap);
-    if (rc) return rc;
-    rc = reset_push_status(e, true);
+    if (rel_hi < kRelTabN && !(e->opt_variant & 256)) {   // a narrow span: the tables by value (variant bit 8: A/B)
+        RelTab tab;
+        memset(&tab, 0, sizeof(tab));
+        tab.n = (int32_t)(rel_hi + 1);
+        for (int32_t j = 0; j < tab.n; ++j) { tab.slot[j] = r2s[j]; tab.code[j] = code[j]; tab.fresh[j] = fresh[j]; }
+        rc = reset_push_status(e, true, &tab);
+    } else {
+        rc = upload(e, e->d_rel2slot, r2s.data(), (sizeof(int32_t) + 2) * kRelCap);
+        if (rc) return rc;
+        rc = reset_push_status(e, true);
+    }
     if (rc) return rc;
     PartArgs pa;
     memset(&pa, 0, sizeof(pa));
@@ -3759,6 +3951,7 @@ static int fire_sessions(fwa_engine* e, int64_t wm, int64_t* nrows) {
     if (rc) return rc;
     if (e->late_rows > 0 && (rc = emit_late_rows(e))) return rc;
     if ((rc = upload(e, &e->d_st->rows, &e->late_rows, 8))) return rc;
+    e->rows_zero = false;
     SessCtr z;
     memset(&z, 0, sizeof(z));
     if ((rc = upload(e, e->d_sctr, &z, sizeof(z)))) return rc;
@@ -3803,8 +3996,85 @@ static int fire_sessions(fwa_engine* e, int64_t wm, int64_t* nrows) {
 // Fire kernel over a list of windows (each a union of slots). raw = 1 emits the accumulators and
 // COUNT(*) instead of the final aggregate values (fwa_drain_partials).
 static int emit_late_rows(fwa_engine* e);
+static int upload_windows(fwa_engine* e, const std::vector<FireWindow>& hw, const std::vector<int32_t>& hs);
+
+// What a watermark's fire may do beyond emitting (fire_walk_kernel). wm: the watermark being advanced to; a fired
+// window whose slice retire_slices(wm) would release is cleared by the fire itself, provided every row fits the output
+// columns (rows from row0 on). check_st: the fire is enqueued behind a push the host has not settled.
+struct FireFuse {
+    int64_t wm = LONG_MIN_J;
+    int64_t row0 = 0;
+    bool check_st = false;
+    std::vector<int32_t> cleared;   // out: the slots the kernel clears unless it finds the push unsettled
+};
+
+// d_st->rows = 0 ahead of a fire: push_reset_kernel already did it unless something fired since the last push.
+static int zero_rows(fwa_engine* e) {
+    if (e->rows_zero && !(e->opt_variant & 256)) return FWA_OK;
+    HIPCHK(e, hipMemsetAsync(&e->d_st->rows, 0, 8, e->stream));
+    return FWA_OK;
+}
+
+// TUMBLE windows of one slot each, few enough for the kernel arguments: fire_walk_kernel (variant bit 8: A/B).
+static int enqueue_fire_walk(fwa_engine* e, const std::vector<FireWindow>& hw, const std::vector<int32_t>& hs, FireFuse* fu) {
+    WalkArgs f;
+    memset(&f, 0, sizeof(f));
+    f.key_table = e->d_keys;
+    f.capacity = e->capacity;
+    f.stride = e->stride;
+    f.o_key = e->o_key;
+    f.o_start = e->o_start;
+    f.o_end = e->o_end;
+    for (int j = 0; j < e->cfg.num_aggs; ++j) { f.o_agg[j] = e->o_agg[j]; f.o_null[j] = e->o_null[j]; }
+    f.out_cap = e->out_cap;
+    f.st = e->d_st;
+    f.touched = e->d_touched;
+    f.nwin = (int32_t)hw.size();
+    f.check_st = fu && fu->check_st ? 1 : 0;
+    // (a) every row fits: windows x keys, the pending push's records counted as new keys
+    const int64_t nk = std::min<int64_t>(e->capacity + 1, (int64_t)e->h_st->n_keys + (e->pend ? e->pend_n : 0));
+    const bool fits = fu && fu->wm != LONG_MIN_J && fu->row0 + (int64_t)hw.size() * std::max<int64_t>(nk, 1) <= e->out_cap;
+    for (size_t i = 0; i < hw.size(); ++i) {
+        WalkWin& w = f.win[i];
+        w.start = hw[i].start;
+        w.end = hw[i].end;
+        w.slot = hs[hw[i].slot_off];
+        w.base = e->slot_ptr[w.slot];
+        int64_t thr;
+        bool always;
+        accept_threshold(e, slice_q(e, w.start), &thr, &always);
+        w.retire = fits && !always && fu->wm >= thr ? 1 : 0;   // (c) as retire_slices: fired but still accepting stays
+        if (w.retire) fu->cleared.push_back(w.slot);
+    }
+    // 8 kids per thread for one or two columns, 4 for more (r07: 2 and 4 kids per thread measured 349 and 198 us per
+    // C2 fire against 182 at 8; 16 kids, 217 VGPRs, the same as 8)
+    const int V = e->nacc <= 2 ? 4 : 2;
+    const unsigned grid = (unsigned)((e->stride + (int64_t)kBlock * 2 * V - 1) / ((int64_t)kBlock * 2 * V));
+    switch (e->nacc) {
+        case 1: fire_walk_kernel<1, 4><<<grid, kBlock, 0, e->stream>>>(f, e->d_ec); break;
+        case 2: fire_walk_kernel<2, 4><<<grid, kBlock, 0, e->stream>>>(f, e->d_ec); break;
+        case 3: fire_walk_kernel<3, 2><<<grid, kBlock, 0, e->stream>>>(f, e->d_ec); break;
+        case 4: fire_walk_kernel<4, 2><<<grid, kBlock, 0, e->stream>>>(f, e->d_ec); break;
+        default: fire_walk_kernel<5, 2><<<grid, kBlock, 0, e->stream>>>(f, e->d_ec); break;
+    }
+    return FWA_OK;
+}
+
 // Enqueue the fire of windows hw (slot lists hs) into the output columns (rows from row0 on; no host wait).
-static int enqueue_fire(fwa_engine* e, const std::vector<FireWindow>& hw, const std::vector<int32_t>& hs, int raw) {
+static int enqueue_fire(fwa_engine* e, const std::vector<FireWindow>& hw, const std::vector<int32_t>& hs, int raw,
+                        FireFuse* fu = nullptr) {
+    e->rows_zero = false;
+    if (fu) fu->cleared.clear();
+    if (!raw && !e->red && e->kind == FWA_TUMBLE && !(e->opt_variant & 256) && e->nacc >= 1 && e->nacc <= 5 && !hw.empty() &&
+        (int)hw.size() <= kWalkMaxWin && std::all_of(hw.begin(), hw.end(), [](const FireWindow& w) { return w.nslots == 1; })) {
+        HIPCHK(e, hipEventRecord(e->ev[2], e->stream));
+        int rc = enqueue_fire_walk(e, hw, hs, fu);
+        if (rc) return rc;
+        HIPCHK(e, hipGetLastError());
+        HIPCHK(e, hipEventRecord(e->ev[3], e->stream));
+        return FWA_OK;
+    }
+    if (int rc = upload_windows(e, hw, hs)) return rc;
     FireArgs f;
     memset(&f, 0, sizeof(f));
     f.key_table = e->d_keys;
@@ -3862,10 +4132,14 @@ static int upload_windows(fwa_engine* e, const std::vector<FireWindow>& hw, cons
     return upload(e, e->d_win, wbuf.data(), wbuf.size());
 }
 
+// retire_wm: the watermark this fire belongs to (its retiring windows may be cleared in the same pass, FireFuse).
 static int launch_fire(fwa_engine* e, const std::vector<FireWindow>& hw, const std::vector<int32_t>& hs, int raw,
-                       int64_t* nrows, int64_t row0 = 0) {
-    int rc = upload_windows(e, hw, hs);
-    if (rc) return rc;
+                       int64_t* nrows, int64_t row0 = 0, int64_t retire_wm = LONG_MIN_J) {
+    int rc = FWA_OK;
+    FireFuse fu;
+    fu.wm = retire_wm;
+    fu.row0 = row0;
+    fu.check_st = e->pend;   // speculative_fire: the push's status comes back with this fire's
     // rows <= windows x distinct keys; n_keys is current: every push ends with a status sync
     const int64_t nkeys = std::max<int64_t>((int64_t)e->h_st->n_keys, 1);
     // Output sizing: rows <= windows x live keys, which is tens of GB for 1e8 keys (C4) although a
@@ -3882,12 +4156,14 @@ static int launch_fire(fwa_engine* e, const std::vector<FireWindow>& hw, const s
         rc = upload(e, &e->d_st->rows, &row0, 8);
         if (rc) return rc;
     } else {
-        HIPCHK(e, hipMemsetAsync(&e->d_st->rows, 0, 8, e->stream));
+        rc = zero_rows(e);
+        if (rc) return rc;
     }
-    rc = enqueue_fire(e, hw, hs, raw);
+    rc = enqueue_fire(e, hw, hs, raw, &fu);
     if (rc) return rc;
-    rc = sync_status(e);
+    rc = sync_status(e);   // (the touched mirror comes back with the flags the fire cleared)
     if (rc) return rc;
+    if (!fu.cleared.empty() && !(fu.check_st && (e->h_st->spill_n || e->h_st->late_fire || e->h_st->error))) e->fused_fires++;
     *nrows = (int64_t)e->h_st->rows;
     if (*nrows > e->out_cap) {   // more rows than the first sizing: grow (2x headroom for the following
         rc = ensure_out(e, std::max<int64_t>(*nrows, std::min<int64_t>(bound, 2 * *nrows)));   // fires), fire again
@@ -4655,6 +4931,7 @@ int fwa_fire_partials(fwa_engine* e, const int64_t* rows, int64_t n, int32_t m, 
     if (int rc1 = wait_input_stream(e)) return rc1;
     HIPCHK(e, hipMemsetAsync(e->d_mf, 0, hdr, e->stream));
     HIPCHK(e, hipMemsetAsync(&e->d_st->rows, 0, 8, e->stream));
+    e->rows_zero = false;
     HIPCHK(e, hipMemsetAsync(&e->d_st->error, 0, 4, e->stream));
     const size_t lds_p = (((size_t)12 * NB + 15) & ~(size_t)15) + (size_t)tile * (8 + 8 * (size_t)m);
     const size_t lds_m = (((size_t)4 * H + 15) & ~(size_t)15) + (size_t)H * (16 + 8 * (size_t)nacc);
@@ -5220,6 +5497,7 @@ static int fire_slide(fwa_engine* e, const std::set<std::pair<int64_t, int64_t>>
     e->rs_valid = false;
   relaunch:
     HIPCHK(e, hipMemsetAsync(&e->d_st->rows, 0, 8, e->stream));
+    e->rows_zero = false;
     FireSlideArgs f;
     memset(&f, 0, sizeof(f));
     f.key_table = e->d_keys;
@@ -5302,7 +5580,7 @@ static int speculative_fire(fwa_engine* e, int64_t wm, int64_t* nrows, bool* ok)
     }
     int rc = FWA_OK;
     if (!hw.empty()) {
-        rc = launch_fire(e, hw, hs, 0, nrows, 0);   // synchronises: the push's status is in h_st too
+        rc = launch_fire(e, hw, hs, 0, nrows, 0, wm);   // synchronises: the push's status is in h_st too
         if (rc) return rc;
     }
     const DevStatus st = *e->h_st;
@@ -5440,7 +5718,7 @@ int fwa_advance_watermark(fwa_engine* e, int64_t wm, fwa_out* out) {
             if (f.nslots > 0) hw.push_back(f);
         }
         if (!hw.empty()) {
-            int rc = launch_fire(e, hw, hs, 0, &nrows, e->late_rows);
+            int rc = launch_fire(e, hw, hs, 0, &nrows, e->late_rows, wm);
             if (rc) return rc;
         }
         int rc = retire_slices(e, wm);
@@ -5495,9 +5773,11 @@ int fwa_advance_watermark_async(fwa_engine* e, int64_t wm) {
         if (!hw.empty() && (need <= e->out_cap || wm != LONG_MAX_J)) {
             int rc = ensure_out(e, need);
             if (rc) return rc;
-            if ((rc = upload_windows(e, hw, hs))) return rc;
-            HIPCHK(e, hipMemsetAsync(&e->d_st->rows, 0, 8, e->stream));
-            if ((rc = enqueue_fire(e, hw, hs, 0))) return rc;
+            FireFuse fu;
+            fu.wm = wm;
+            fu.check_st = true;
+            if ((rc = zero_rows(e))) return rc;
+            if ((rc = enqueue_fire(e, hw, hs, 0, &fu))) return rc;
             HIPCHK(e, hipMemcpyAsync(e->h_af_rows, &e->d_st->rows, 8, hipMemcpyDeviceToHost, e->stream));
             HIPCHK(e, hipEventRecord(e->ev_af, e->stream));
             if ((rc = wait_status_event(e))) return rc;   // the push's status; the fire keeps running
@@ -5505,7 +5785,10 @@ int fwa_advance_watermark_async(fwa_engine* e, int64_t wm) {
             if (st.spill_n == 0 && st.late_fire == 0 && st.error == 0) {
                 e->af_gpu = true;
                 e->af_pend = true;
-                if ((rc = retire_slices(e, wm))) return rc;   // resets enqueued behind the fire
+                // slots the fire cleared itself: the mirror just read predates the fire
+                for (int32_t s : fu.cleared) e->touched[s] = 0;
+                if (!fu.cleared.empty()) e->fused_fires++;
+                if ((rc = retire_slices(e, wm))) return rc;   // the other resets, enqueued behind the fire
                 if ((rc = settle_push(e))) return rc;      // no wait (st_ready)
                 e->wm = wm;
                 return FWA_OK;
@@ -5620,6 +5903,8 @@ int fwa_get_option(const fwa_engine* e, int32_t option, int64_t* value) {
         case FWA_OPT_SLIDE_CARRIED: *value = e->rs_used; return FWA_OK;
         case FWA_OPT_FIRE_PARTIALS: *value = e->mf_calls - e->mf_fallbacks; return FWA_OK;
         case FWA_OPT_DEC_WRAP_NULL: *value = e->opt_dec_wrap_null; return FWA_OK;
+        case FWA_OPT_FUSED_FIRES: *value = e->fused_fires; return FWA_OK;
+        case FWA_OPT_RESET_LAUNCHES: *value = e->reset_launches; return FWA_OK;
         default: return FWA_E_ARG;
     }
 }

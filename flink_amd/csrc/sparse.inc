@@ -1102,6 +1102,7 @@ static int sp_fire(fwa_engine* e, const std::vector<int64_t>& qs, int raw, bool 
     f.out_cap = e->out_cap;
     f.st = e->d_st;
     HIPCHK(e, hipMemsetAsync(&e->d_st->rows, 0, 8, e->stream));
+    e->rows_zero = false;
     HIPCHK(e, hipEventRecord(e->ev[2], e->stream));
     auto launch = [&](auto na) {
         constexpr int NA = decltype(na)::value;

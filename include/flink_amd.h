@@ -520,14 +520,21 @@ enum fwa_option {
     FWA_OPT_SESSION_PATH = 11,   /* read only: the path of the last session push -- 0 general, 1 sort-based cells,
                                     2 cell pre-aggregation (fwa_get_option) */
     FWA_OPT_INGEST_VARIANT = 12, /* diagnostic A/B switches of the ingest kernels (0 default); bit 0: the combiner
-                                    reads a slot it merges into even when no record reached it yet */
+                                    reads a slot it merges into even when no record reached it yet; bit 8 (256): the
+                                    tumbling fire as one kernel block per (window, key chunk) with an uploaded window
+                                    table, a memset of its row counter and reset_slots_kernel for the retired slots,
+                                    instead of the one-pass fire that retires its slots itself, and every push uploads
+                                    its slice tables instead of passing narrow ones in the kernel arguments */
     FWA_OPT_SLIDE_CARRIED = 13,  /* read only: sliding fires whose first window reused the previous run's carried
                                     window sums (fwa_get_option; set: 0 disables the reuse, 1 enables it, default) */
     FWA_OPT_FIRE_PARTIALS = 14,  /* read only: fwa_fire_partials calls that merged and fired on chip (fwa_get_option;
                                     set: 0 sends every call through fwa_push_partials + fwa_advance_watermark) */
-    FWA_OPT_DEC_WRAP_NULL = 15   /* 1: a DECIMAL SUM / AVG over 2^32 or more records of one window is emitted NULL and
+    FWA_OPT_DEC_WRAP_NULL = 15,  /* 1: a DECIMAL SUM / AVG over 2^32 or more records of one window is emitted NULL and
                                   * counted (fwa_stats.dec_inexact); 0 (default): that watermark step fails
                                   * (FWA_E_UNSUPPORTED) instead of a silently different result */
+    FWA_OPT_FUSED_FIRES = 16,    /* read only: watermark fires that restored the identities of the slots they retired in
+                                    the same pass (fwa_get_option) */
+    FWA_OPT_RESET_LAUNCHES = 17  /* read only: launches of the separate slot-reset kernel (fwa_get_option) */
 };
 int fwa_set_option(fwa_engine* e, int32_t option, int64_t value);
 /* The option's effective value: for the tri-state options 1 if the handle currently takes that path (forced, or
