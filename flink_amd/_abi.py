@@ -29,6 +29,7 @@ AGG_KINDS = {
     "SUM_I32": 18, "MIN_I32": 19, "MAX_I32": 20, "FIRST_64": 21, "FIRST_32": 22,
     "MINBY_I64": 23, "MAXBY_I64": 24, "MINBY_I32": 25, "MAXBY_I32": 26, "MINBY_F64": 27, "MAXBY_F64": 28,
     "MINBY_F32": 29, "MAXBY_F32": 30, "SEL_64": 31, "SEL_32": 32,
+    "COUNT_DISTINCT": 33,    # COUNT(DISTINCT col): 8-byte values compared by their bits (Table TUMBLE)
 }
 DEC_KINDS = ("SUM_DEC", "AVG_DEC", "SUM_DEC128", "AVG_DEC128")
 AGG_NAMES = {v: k for k, v in AGG_KINDS.items()}
@@ -43,6 +44,7 @@ AGG_RESULT_DTYPE = {
     "SUM_I32": "i4", "MIN_I32": "i4", "MAX_I32": "i4", "FIRST_64": "i8", "FIRST_32": "i4",
     "MINBY_I64": "i8", "MAXBY_I64": "i8", "MINBY_I32": "i4", "MAXBY_I32": "i4", "MINBY_F64": "f8", "MAXBY_F64": "f8",
     "MINBY_F32": "f4", "MAXBY_F32": "f4", "SEL_64": "i8", "SEL_32": "i4",
+    "COUNT_DISTINCT": "i8",
 }
 # numpy dtype of each aggregate's INPUT column (None: no input)
 AGG_INPUT_DTYPE = {
@@ -53,6 +55,7 @@ AGG_INPUT_DTYPE = {
     "SUM_I32": "i4", "MIN_I32": "i4", "MAX_I32": "i4", "FIRST_64": "i8", "FIRST_32": "i4",
     "MINBY_I64": "i8", "MAXBY_I64": "i8", "MINBY_I32": "i4", "MAXBY_I32": "i4", "MINBY_F64": "f8", "MAXBY_F64": "f8",
     "MINBY_F32": "f4", "MAXBY_F32": "f4", "SEL_64": "i8", "SEL_32": "i4",
+    "COUNT_DISTINCT": "i8",
 }
 
 

@@ -1,0 +1,659 @@
+// COUNT(DISTINCT col) over Table TUMBLE windows (include/flink_amd.h, FWA_COUNT_DISTINCT) -- included by engine.hip.
+//
+// Reference: the planner expands COUNT(DISTINCT c) into a distinct view (a MapView<value, bitmap> per (key, slice) in
+// the accumulator, DistinctInfo / AggsHandlerCodeGenerator.addReusableDistinctAccumulators) and counts a value the first
+// time the view sees it; NULL values are never added (Count1AggFunction over the distinct filter).
+//
+// Design: a tumbling window is one slice, so COUNT(DISTINCT c) of a (key, window) is the SUM(BIGINT) of a 0/1 column
+// "this record is the first one of its (key, window, value)". fwa_create rewrites COUNT_DISTINCT(c) in place into
+// SUM_I64(m) over a marked column m that only the engine writes (dist_plan, the sibling of dec_plan), and every push
+// first runs distinct_mark_kernel over the batch: it inserts (key, value, slice, column) into one device-resident
+// open-addressing set per handle and writes mark[i] = 1 iff this insert created the entry. Phase P / A, the fire
+// kernels, record lists and snapshots then see an ordinary 64-bit sum. A window of several slices (HOP, CUMULATE,
+// SESSION) would need the union of per-slice sets at the fire, which is not a sum: those are refused.
+//
+// The set. One 32-byte aligned entry per slot, three 64-bit words used (the fourth pads the entry to one 32-byte
+// sector, so a probe is one aligned vector load):
+//   word 0  key   (a zero key is stored as 1 with tag bit 3 set)
+//   word 1  value (a zero value is stored as 1 with tag bit 4 set)
+//   word 2  tag = q << 6 | 1 << 5 | value-was-zero << 4 | key-was-zero << 3 | marked column (3 bits)
+// EMPTY = 0 for every word; bit 5 keeps a tag from being 0. The slice number q keeps 58 bits: |q| <= 2^63 / size, so
+// windows of 64 ms and more can never alias (smaller ones are refused at fwa_create).
+// Insert: words are claimed in order with atomicCAS(word, EMPTY, mine) and never change afterwards. At each word a
+// CAS that returns EMPTY or my own word goes on to the next word of the same slot; any other value moves to the next
+// slot (linear probing from a 64-bit mix of the three words). The lane whose tag CAS returned EMPTY created the entry;
+// a lane that finds its own tag is a duplicate. Equal entries walk the same slots and meet the same immutable words,
+// so exactly one lane reports "new" and an entry never lands in two slots; nothing spins or waits for another lane.
+// A plain 32-byte load precedes the CASes: duplicates (the common case) cost no atomic; a stale load can only show
+// EMPTY where a word is set by now, which falls through to the CAS.
+// Capacity is decided on the host before each launch: bound = an upper bound of occupied slots (previous bound +
+// records x marked columns) stays <= slots / 2, so a launch cannot fill the table. The marking pass also counts the
+// entries it created (one atomic per wave); the count comes back with the push and replaces the "+ records" of that
+// push, so pushes of mostly known values do not inflate the bound. When the bound would not fit,
+// distinct_count_kernel counts the entries of windows that have not fired (one atomic per block) and the table is rebuilt
+// at 2 x (live + this batch) slots (rounded up to a power of two): into a new allocation when the size changes
+// (distinct_rebuild_kernel re-inserts the live entries), in place when it does not (distinct_extract_kernel moves the
+// live entries to a side buffer and clears every slot in the same pass, distinct_insert_side_kernel puts them back: no
+// allocation of the table's size in the steady state). The bound becomes the exact count. Firing a window costs
+// nothing: its entries are garbage the next rebuild drops, so the set holds live entries + one batch (x <= 4 for the
+// load factor and the rounding).
+
+struct DistinctPlan {
+    fwa_config ucfg;                       // the caller's configuration (fwa_get_config)
+    int32_t nd = 0;                        // marked columns (one per distinct source column)
+    int32_t src[FWA_MAX_AGGS] = {};        // marked column d: the caller's value column
+    int32_t mcol[FWA_MAX_AGGS] = {};       // ... and the internal value-column index of its 0/1 column
+    int64_t mask = 0;                      // bit j: the caller's aggregate j is COUNT_DISTINCT (snapshot header)
+    unsigned long long* d_tab = nullptr;   // the set, [slots][4]
+    int64_t slots = 0, first_slots = 0;    // first_slots: FWA_OPT_DISTINCT_SLOTS (0: sized from the first push)
+    int64_t bound = 0;                     // upper bound of occupied slots
+    int64_t live = 0, rebuilds = 0;        // entries counted at the last rebuild; rebuilds so far
+    unsigned long long* d_mark = nullptr;  // marked columns, [nd][mark_cap]
+    int64_t mark_cap = 0;
+    char* d_stage = nullptr;               // host pushes: every input column, staged once
+    size_t stage_bytes = 0;
+    unsigned long long* d_ctr = nullptr;   // [0] entries counted / created, [1] inserts that found no slot,
+    unsigned long long* h_ctr = nullptr;   // [2] entries the last marking pass created (h_ctr[2]: its pinned landing)
+    unsigned int* d_bcnt = nullptr;        // table scans: live entries per block [kDistScanGrid], then (8-byte aligned)
+    unsigned long long* d_bpre = nullptr;  // ... their exclusive prefix [kDistScanGrid]
+    unsigned long long* d_side = nullptr;  // in-place rebuild: the live entries, [3][side_cap]
+    int64_t side_cap = 0;
+    hipEvent_t ev[3] = {};                 // marking pass begin / end (timed), its created-count copy
+    bool timing = false;                   // ev[0..1] hold a marking pass not yet added to ingest_ms
+    int64_t last_add = 0;                  // the last marking pass's share of `bound`, until its exact count replaces it
+};
+
+namespace {
+
+const char* const kDistNoPartials = "partial accumulators of COUNT(DISTINCT): a distinct count is not mergeable without "
+                                    "shipping the sets";
+constexpr int64_t kDistMinSlots = 1 << 12;
+constexpr int64_t kDistMinSize = 64;       // ms: the tag keeps 58 bits of the slice number
+
+__device__ __forceinline__ uint64_t dist_hash(uint64_t k, uint64_t v, uint64_t t) {
+    return jm::mix64(k ^ jm::mix64(v ^ jm::mix64(t)));
+}
+
+__host__ __device__ __forceinline__ uint64_t dist_tag(int64_t q, uint64_t key, uint64_t val, int d) {
+    return ((uint64_t)q << 6) | 32ull | (val == 0 ? 16ull : 0ull) | (key == 0 ? 8ull : 0ull) | (uint64_t)(d & 7);
+}
+__host__ __device__ __forceinline__ int64_t dist_tag_q(uint64_t tag) { return (int64_t)tag >> 6; }
+
+// 1: this call created the entry, 0: it was there, -1: no slot (the host's bound makes that impossible)
+__device__ __forceinline__ int dist_insert(unsigned long long* tab, uint64_t smask, uint64_t k, uint64_t v, uint64_t t) {
+    uint64_t i = dist_hash(k, v, t) & smask;
+    for (uint64_t probe = 0; probe <= smask; ++probe, i = (i + 1) & smask) {
+        unsigned long long* s = tab + 4 * i;
+        const ulonglong2 kv = *reinterpret_cast<const ulonglong2*>(s);
+        unsigned long long c = kv.x;
+        if (c == 0ull) { c = atomicCAS(s, 0ull, (unsigned long long)k); if (c == 0ull) c = k; }
+        if (c != k) continue;
+        c = kv.y;
+        if (c == 0ull) { c = atomicCAS(s + 1, 0ull, (unsigned long long)v); if (c == 0ull) c = v; }
+        if (c != v) continue;
+        c = s[2];
+        if (c == 0ull) { c = atomicCAS(s + 2, 0ull, (unsigned long long)t); if (c == 0ull) return 1; }
+        if (c == t) return 0;
+    }
+    return -1;
+}
+
+struct DistMarkArgs {
+    const int64_t* keys;
+    const int64_t* ts;
+    const int64_t* src[FWA_MAX_AGGS];      // source value column of marked column d (8-byte values, compared by bits)
+    const uint8_t* nul[FWA_MAX_AGGS];      // its NULL flags (nullptr: none)
+    unsigned long long* mark[FWA_MAX_AGGS];
+    int32_t nd;
+    int64_t n;
+    int64_t q_min;                         // first slice whose window has not fired at the handle's watermark
+    unsigned long long* tab;
+    uint64_t smask;                        // slots - 1
+    unsigned long long* ctr;
+};
+
+// One thread per record: the slice number as the ingest kernels compute it, then one set insert per marked column.
+__global__ void __launch_bounds__(256) distinct_mark_kernel(DistMarkArgs a, const EngineConst* __restrict__ cp) {
+    const EngineConst& c = *cp;
+    unsigned int created = 0;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * blockDim.x) {
+        const uint64_t key = (uint64_t)a.keys[i];
+        const int64_t q = sp_slice(c, assign_ts(c, a.ts[i]));
+        for (int d = 0; d < a.nd; ++d) {
+            unsigned long long m = 0ull;
+            if (q >= a.q_min && !(a.nul[d] && a.nul[d][i])) {
+                const uint64_t v = (uint64_t)a.src[d][i];
+                const int r = dist_insert(a.tab, a.smask, key ? key : 1ull, v ? v : 1ull, dist_tag(q, key, v, d));
+                if (r < 0) atomicAdd(a.ctr + 1, 1ull);
+                m = r > 0 ? 1ull : 0ull;
+                created += r > 0 ? 1u : 0u;
+            }
+            a.mark[d][i] = m;
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) created += __shfl_down(created, o);    // the whole wave is back here
+    if ((threadIdx.x & 63) == 0 && created) atomicAdd(a.ctr + 2, (unsigned long long)created);
+}
+
+// The scans of the table give block b the slots [b * chunk, (b + 1) * chunk): the count pass leaves each block's live
+// count, from which the extract pass knows where the block's entries go without a shared cursor (one atomic on one
+// word per wave and iteration capped both passes at the rate of that word: ~50 ms for 2^28 slots).
+constexpr int kDistScanGrid = 4096;
+__device__ __forceinline__ void dist_block_range(int64_t slots, int64_t* lo, int64_t* hi) {
+    const int64_t chunk = (((slots + gridDim.x - 1) / gridDim.x) + 255) & ~(int64_t)255;
+    *lo = (int64_t)blockIdx.x * chunk;
+    *hi = *lo + chunk < slots ? *lo + chunk : slots;
+}
+
+// Entries of windows that have not fired: per block into bcnt[], and their sum with one atomic per block.
+__global__ void __launch_bounds__(256) distinct_count_kernel(const unsigned long long* tab, int64_t slots, int64_t q_min,
+                                                            unsigned long long* ctr, unsigned int* bcnt) {
+    __shared__ unsigned int tot;
+    if (threadIdx.x == 0) tot = 0;
+    __syncthreads();
+    int64_t lo, hi;
+    dist_block_range(slots, &lo, &hi);
+    unsigned int mine = 0;
+    for (int64_t i = lo + threadIdx.x; i < hi; i += 256) {
+        const unsigned long long t = tab[4 * i + 2];
+        mine += (t != 0ull && dist_tag_q(t) >= q_min) ? 1u : 0u;
+    }
+    for (int o = 32; o > 0; o >>= 1) mine += __shfl_down(mine, o);
+    if ((threadIdx.x & 63) == 0 && mine) atomicAdd(&tot, mine);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        bcnt[blockIdx.x] = tot;
+        if (tot) atomicAdd(ctr, (unsigned long long)tot);
+    }
+}
+
+// Exclusive prefix of the nb block counts (one wave: 64 runs of consecutive blocks).
+__global__ void __launch_bounds__(64) distinct_prefix_kernel(const unsigned int* bcnt, int nb, unsigned long long* bpre) {
+    const int lane = threadIdx.x, per = (nb + 63) / 64;
+    const int lo = lane * per, hi = lo + per < nb ? lo + per : nb;
+    unsigned long long sum = 0;
+    for (int j = lo; j < hi; ++j) sum += bcnt[j];
+    unsigned long long incl = sum;
+    for (int o = 1; o < 64; o <<= 1) {
+        const unsigned long long up = __shfl_up(incl, o);
+        if (lane >= o) incl += up;
+    }
+    unsigned long long run = incl - sum;
+    for (int j = lo; j < hi; ++j) { bpre[j] = run; run += bcnt[j]; }
+}
+
+// Rebuild into a new table: the entries of unfired windows re-inserted; ctr[0] receives the entries created there (the
+// exact live count), one atomic per wave.
+__global__ void __launch_bounds__(256) distinct_rebuild_kernel(const unsigned long long* tab, int64_t slots, int64_t q_min,
+                                                              unsigned long long* ntab, uint64_t nsmask,
+                                                              unsigned long long* ctr) {
+    unsigned int made = 0;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < slots; i += (int64_t)gridDim.x * blockDim.x) {
+        const ulonglong2 kv = *reinterpret_cast<const ulonglong2*>(tab + 4 * i);
+        const unsigned long long t = tab[4 * i + 2];
+        if (t != 0ull && dist_tag_q(t) >= q_min) {
+            const int r = dist_insert(ntab, nsmask, kv.x, kv.y, t);
+            if (r < 0) atomicAdd(ctr + 1, 1ull);
+            made += r > 0 ? 1u : 0u;
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) made += __shfl_down(made, o);
+    if ((threadIdx.x & 63) == 0 && made) atomicAdd(ctr, (unsigned long long)made);
+}
+
+// In-place rebuild, first half: block b's entries of unfired windows move to side[3][cap] from bpre[b] on (an LDS
+// cursor orders them inside the block) and every slot is cleared in the same pass (each thread owns its slot: nothing
+// inserts meanwhile). ctr[0] receives the entries moved.
+__global__ void __launch_bounds__(256) distinct_extract_kernel(unsigned long long* tab, int64_t slots, int64_t q_min,
+                                                              unsigned long long* side, int64_t cap,
+                                                              const unsigned long long* bpre, unsigned long long* ctr) {
+    __shared__ unsigned int cur;
+    if (threadIdx.x == 0) cur = 0;
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int64_t base = (int64_t)bpre[blockIdx.x];
+    int64_t lo, hi;
+    dist_block_range(slots, &lo, &hi);
+    for (int64_t i0 = lo; i0 < hi; i0 += 256) {           // (uniform per block: every lane takes every iteration)
+        const int64_t i = i0 + threadIdx.x;
+        ulonglong2 kv = make_ulonglong2(0ull, 0ull);
+        unsigned long long t = 0ull;
+        if (i < hi) {
+            kv = *reinterpret_cast<const ulonglong2*>(tab + 4 * i);
+            t = tab[4 * i + 2];
+            if (kv.x | kv.y | t) {
+                *reinterpret_cast<ulonglong2*>(tab + 4 * i) = make_ulonglong2(0ull, 0ull);
+                tab[4 * i + 2] = 0ull;
+            }
+        }
+        const bool livee = t != 0ull && dist_tag_q(t) >= q_min;
+        const unsigned long long b = __ballot(livee);
+        if (!b) continue;                                  // (wave-uniform)
+        unsigned int off = 0;
+        if (lane == 0) off = atomicAdd(&cur, (unsigned int)__popcll(b));
+        off = __shfl(off, 0);
+        if (livee) {
+            const int64_t pos = base + off + __popcll(b & ((1ull << lane) - 1ull));
+            if (pos < cap) { side[pos] = kv.x; side[cap + pos] = kv.y; side[2 * cap + pos] = t; }
+            else atomicAdd(ctr + 1, 1ull);
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && cur) atomicAdd(ctr, (unsigned long long)cur);
+}
+
+// Restore and the in-place rebuild's second half: entries given as their three stored words (w[3][n]), inserted
+// without marking.
+__global__ void __launch_bounds__(256) distinct_insert_side_kernel(const unsigned long long* w, int64_t stride, int64_t n,
+                                                                  unsigned long long* tab, uint64_t smask,
+                                                                  unsigned long long* ctr) {
+    unsigned int made = 0;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int r = dist_insert(tab, smask, w[i], w[stride + i], w[2 * stride + i]);
+        if (r < 0) atomicAdd(ctr + 1, 1ull);
+        made += r > 0 ? 1u : 0u;
+    }
+    for (int o = 32; o > 0; o >>= 1) made += __shfl_down(made, o);
+    if ((threadIdx.x & 63) == 0 && made) atomicAdd(ctr, (unsigned long long)made);
+}
+
+// ---- host ----
+
+bool has_distinct(const fwa_config* c) {
+    for (int j = 0; j < c->num_aggs && j < FWA_MAX_AGGS; ++j) if (c->aggs[j].kind == FWA_COUNT_DISTINCT) return true;
+    return false;
+}
+
+// The internal configuration of a handle with COUNT(DISTINCT) aggregates: each one rewritten in place into SUM_I64 of
+// its marked column (same position, same result type: no output remapping). 0 or an fwa_status with *why set.
+int dist_plan(const fwa_config* u, DistinctPlan* P, fwa_config* icfg, std::string* why) {
+    P->ucfg = *u;
+    *icfg = *u;
+    if (u->num_aggs < 0 || u->num_aggs > FWA_MAX_AGGS) return FWA_E_ARG;
+    for (int j = 0; j < u->num_aggs; ++j) {
+        const fwa_agg_spec& s = u->aggs[j];
+        if (s.kind < 0 || s.kind >= FWA_AGG_KIND_COUNT) return FWA_E_ARG;
+        if (s.kind != FWA_COUNT && (s.col < 0 || s.col >= FWA_MAX_COLS)) return FWA_E_ARG;
+    }
+    auto no = [&](const char* m) { *why = std::string("COUNT(DISTINCT): ") + m; return FWA_E_UNSUPPORTED; };
+    if (u->window_kind != FWA_TUMBLE)
+        return no("only TUMBLE windows (a window of several slices needs the union of their sets, which is not additive)");
+    if (u->semantics != FWA_SEM_TABLE) return no("a Table aggregate (FWA_SEM_TABLE)");
+    if (u->flags & FWA_CFG_REDUCE) return no("not a DataStream reduction");
+    if (u->key_kind == FWA_KEY_PREHASHED)
+        return no("PREHASHED keys are not supported (the set keeps no hash per entry to place it in a key group)");
+    if (u->size_ms > 0 && u->size_ms < kDistMinSize) return no("windows shorter than 64 ms are not supported");
+    // value-column indices: a source column that only COUNT(DISTINCT) reads hands its index to its marked column;
+    // otherwise the marked column takes an index nothing else uses
+    bool used[FWA_MAX_COLS] = {}, isrc[FWA_MAX_COLS] = {};
+    for (int j = 0; j < u->num_aggs; ++j) {
+        const fwa_agg_spec& s = u->aggs[j];
+        if (s.kind == FWA_COUNT_DISTINCT) isrc[s.col] = true;
+        else if (s.kind != FWA_COUNT) used[s.col] = true;     // COUNT(col) reads the column's NULL flags
+    }
+    int mof[FWA_MAX_COLS];
+    for (int c = 0; c < FWA_MAX_COLS; ++c) mof[c] = -1;
+    for (int c = 0; c < FWA_MAX_COLS; ++c) if (isrc[c] && !used[c]) mof[c] = c;
+    for (int c = 0; c < FWA_MAX_COLS; ++c) {
+        if (!isrc[c] || mof[c] >= 0) continue;
+        for (int m = 0; m < FWA_MAX_COLS && mof[c] < 0; ++m) {
+            if (used[m] || isrc[m]) continue;
+            mof[c] = m;
+            used[m] = true;
+        }
+        if (mof[c] < 0) return no("no free value column for the marked column (FWA_MAX_COLS)");
+    }
+    for (int j = 0; j < u->num_aggs; ++j) {
+        const fwa_agg_spec& s = u->aggs[j];
+        if (s.kind != FWA_COUNT_DISTINCT) continue;
+        P->mask |= (int64_t)1 << j;
+        int d = -1;
+        for (int i = 0; i < P->nd; ++i) if (P->src[i] == s.col) d = i;
+        if (d < 0) {
+            d = P->nd++;
+            P->src[d] = s.col;
+            P->mcol[d] = mof[s.col];
+        }
+        icfg->aggs[j].kind = FWA_SUM_I64;
+        icfg->aggs[j].col = P->mcol[d];
+        icfg->nullable_cols &= ~(1 << P->mcol[d]);            // the marked column holds no NULLs
+    }
+    return FWA_OK;
+}
+
+void dist_free(DistinctPlan* P) {
+    if (!P) return;
+    for (void* p : {(void*)P->d_tab, (void*)P->d_mark, (void*)P->d_stage, (void*)P->d_ctr, (void*)P->d_side, (void*)P->d_bcnt,
+                    (void*)P->d_bpre})
+        if (p) (void)hipFree(p);
+    if (P->h_ctr) (void)hipHostFree(P->h_ctr);
+    for (hipEvent_t ev : P->ev) if (ev) (void)hipEventDestroy(ev);
+    delete P;
+}
+
+// First slice whose window has not fired at the handle's watermark (every lower slice drops its records), or
+// LONG_MIN_J when that is not known cheaply: skipping lower slices only keeps garbage out of the set.
+int64_t dist_qmin(const fwa_engine* e) {
+    if (e->wm == LONG_MIN_J) return LONG_MIN_J;
+    auto fired = [&](int64_t q) {
+        int64_t thr;
+        bool always;
+        accept_threshold(e, q, &thr, &always);
+        return !always && e->wm >= thr;
+    };
+    const int64_t lw = e->tz.empty() ? e->wm : jm::tz_to_local(e->tz.data(), (int)(e->tz.size() / 2), e->wm);
+    int64_t q = slice_q(e, lw);
+    if (q > LONG_MAX_J - 2 || q < LONG_MIN_J + 70) return LONG_MIN_J;
+    q += 1;
+    for (int step = 0; step < 64; ++step, --q) if (fired(q - 1)) return q;
+    return LONG_MIN_J;
+}
+
+int dist_counters(fwa_engine* e) {
+    DistinctPlan* P = e->dist;
+    if (P->d_ctr) return FWA_OK;
+    HIPCHK(e, hipMalloc(&P->d_ctr, 32));
+    HIPCHK(e, hipHostMalloc((void**)&P->h_ctr, 32));
+    memset(P->h_ctr, 0, 32);
+    HIPCHK(e, hipMemsetAsync(P->d_ctr, 0, 32, e->stream));
+    HIPCHK(e, hipMalloc(&P->d_bcnt, sizeof(unsigned int) * kDistScanGrid));
+    HIPCHK(e, hipMalloc(&P->d_bpre, sizeof(unsigned long long) * kDistScanGrid));
+    for (hipEvent_t& ev : P->ev) HIPCHK(e, hipEventCreate(&ev));
+    return FWA_OK;
+}
+
+// Read ctr[0] (and check ctr[1]) after the work enqueued so far; synchronises.
+int dist_read_counter(fwa_engine* e, int64_t* out) {
+    DistinctPlan* P = e->dist;
+    HIPCHK(e, hipMemcpyAsync(P->h_ctr, P->d_ctr, 16, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    if (P->h_ctr[1]) return fail(e, FWA_E_STATE, "COUNT(DISTINCT) set overflowed its bound");
+    *out = (int64_t)P->h_ctr[0];
+    return FWA_OK;
+}
+
+int64_t dist_pow2(int64_t x) {
+    int64_t p = 64;
+    while (p < x) p <<= 1;
+    return p;
+}
+
+// The entries of windows that have not fired at the handle's watermark (and, per scan block, in d_bcnt); synchronises.
+int dist_count_live(fwa_engine* e, int64_t q_min, int grid, int64_t* livee) {
+    DistinctPlan* P = e->dist;
+    HIPCHK(e, hipMemsetAsync(P->d_ctr, 0, 8, e->stream));
+    distinct_count_kernel<<<grid, 256, 0, e->stream>>>(P->d_tab, P->slots, q_min, P->d_ctr, P->d_bcnt);
+    HIPCHK(e, hipGetLastError());
+    return dist_read_counter(e, livee);
+}
+
+// In-place rebuild after dist_count_live: the live entries through the side buffer (which keeps them, [3][side_cap],
+// for the snapshot to read), every other slot cleared.
+int dist_compact(fwa_engine* e, int64_t q_min, int grid, int64_t livee) {
+    DistinctPlan* P = e->dist;
+    if (livee > P->side_cap) {
+        if (P->d_side) HIPCHK(e, hipFree(P->d_side));
+        P->d_side = nullptr;
+        P->side_cap = 0;
+        const int64_t cap = std::max<int64_t>(livee + livee / 4, 1 << 12);
+        HIPCHK(e, hipMalloc(&P->d_side, 24 * (size_t)cap));
+        P->side_cap = cap;
+    }
+    int64_t taken = 0, moved = 0;
+    HIPCHK(e, hipMemsetAsync(P->d_ctr, 0, 8, e->stream));
+    distinct_prefix_kernel<<<1, 64, 0, e->stream>>>(P->d_bcnt, grid, P->d_bpre);
+    HIPCHK(e, hipGetLastError());
+    distinct_extract_kernel<<<grid, 256, 0, e->stream>>>(P->d_tab, P->slots, q_min, P->d_side, P->side_cap, P->d_bpre,
+                                                         P->d_ctr);
+    HIPCHK(e, hipGetLastError());
+    if (int rc = dist_read_counter(e, &taken)) return rc;
+    if (taken != livee) return fail(e, FWA_E_STATE, "COUNT(DISTINCT) rebuild lost entries");
+    if (taken > 0) {
+        HIPCHK(e, hipMemsetAsync(P->d_ctr, 0, 8, e->stream));
+        distinct_insert_side_kernel<<<grid_for(taken, 4096), 256, 0, e->stream>>>(P->d_side, P->side_cap, taken, P->d_tab,
+                                                                                  (uint64_t)P->slots - 1, P->d_ctr);
+        HIPCHK(e, hipGetLastError());
+        if (int rc = dist_read_counter(e, &moved)) return rc;
+        if (moved != livee) return fail(e, FWA_E_STATE, "COUNT(DISTINCT) rebuild lost entries");
+    }
+    P->live = livee;
+    P->rebuilds++;
+    return FWA_OK;
+}
+
+// Make room for `add` more inserts: bound + add <= slots / 2, rebuilding the table from its live entries otherwise.
+int dist_reserve(fwa_engine* e, int64_t add) {
+    DistinctPlan* P = e->dist;
+    if (int rc = dist_counters(e)) return rc;
+    if (!P->d_tab) {
+        P->slots = P->first_slots > 0 ? P->first_slots : dist_pow2(std::max<int64_t>(2 * add, kDistMinSlots));
+        HIPCHK(e, hipMalloc(&P->d_tab, 32 * (size_t)P->slots));
+        HIPCHK(e, hipMemsetAsync(P->d_tab, 0, 32 * (size_t)P->slots, e->stream));
+        P->bound = 0;
+    }
+    if (P->last_add) {   // the last marking pass's exact count (its copy was enqueued behind it) replaces its estimate
+        HIPCHK(e, hipEventSynchronize(P->ev[2]));
+        const int64_t made = (int64_t)P->h_ctr[2];
+        if (made >= 0 && made <= P->last_add) P->bound -= P->last_add - made;
+        P->last_add = 0;
+    }
+    if (P->bound + add <= P->slots / 2) { P->bound += add; return FWA_OK; }
+    const int64_t q_min = dist_qmin(e);
+    const int grid = grid_for(P->slots, kDistScanGrid);
+    int64_t livee = 0;
+    if (int rc = dist_count_live(e, q_min, grid, &livee)) return rc;
+    const int64_t nslots = dist_pow2(std::max<int64_t>(2 * (livee + add), 64));
+    if (nslots == P->slots) {   // same size: in place, through the side buffer
+        if (int rc = dist_compact(e, q_min, grid, livee)) return rc;
+        P->bound = livee + add;
+        return FWA_OK;
+    }
+    unsigned long long* ntab = nullptr;
+    HIPCHK(e, hipMalloc(&ntab, 32 * (size_t)nslots));
+    hipError_t r = hipMemsetAsync(ntab, 0, 32 * (size_t)nslots, e->stream);
+    if (r == hipSuccess) r = hipMemsetAsync(P->d_ctr, 0, 8, e->stream);
+    if (r == hipSuccess) {
+        distinct_rebuild_kernel<<<grid, 256, 0, e->stream>>>(P->d_tab, P->slots, q_min, ntab, (uint64_t)nslots - 1, P->d_ctr);
+        r = hipGetLastError();
+    }
+    int64_t moved = 0;
+    int rc = r == hipSuccess ? dist_read_counter(e, &moved) : fail(e, FWA_E_DEVICE, hipGetErrorString(r));
+    if (rc || moved != livee) {
+        (void)hipFree(ntab);
+        return rc ? rc : fail(e, FWA_E_STATE, "COUNT(DISTINCT) rebuild lost entries");
+    }
+    HIPCHK(e, hipFree(P->d_tab));
+    P->d_tab = ntab;
+    P->slots = nslots;
+    P->live = moved;
+    P->bound = moved + add;
+    P->rebuilds++;
+    return FWA_OK;
+}
+
+// The marking pass's device time, once its events completed, goes to ingest_ms (like the index column of reductions).
+void dist_collect_timing(fwa_engine* e) {
+    DistinctPlan* P = e->dist;
+    if (!P || !P->timing || hipEventQuery(P->ev[1]) != hipSuccess) return;
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, P->ev[0], P->ev[1]) == hipSuccess) e->ingest_ms += ms;
+    P->timing = false;
+}
+
+size_t dist_in_width(int kind) { return is_dec_kind(kind) ? (size_t)dec_width(kind) : type_size(kind); }
+
+// Mark the batch. On return *keys / *ts, vals[] and nulls[] are device pointers laid out for the internal
+// configuration (the marked columns at their indices); host inputs are staged once, here.
+int dist_mark(fwa_engine* e, const int64_t** keys, const int64_t** ts, const void* const* val_cols,
+              const uint8_t* const* null_cols, int64_t n, bool device, const void** vals, const uint8_t** nulls) {
+    DistinctPlan* P = e->dist;
+    const fwa_config& u = P->ucfg;
+    dist_collect_timing(e);
+    for (int c = 0; c < FWA_MAX_COLS; ++c) { vals[c] = nullptr; nulls[c] = nullptr; }
+    size_t width[FWA_MAX_COLS] = {};
+    for (int j = 0; j < u.num_aggs; ++j) {
+        const fwa_agg_spec& s = u.aggs[j];
+        if (s.kind == FWA_COUNT || s.kind == FWA_COUNT_COL) continue;
+        if (!val_cols || !val_cols[s.col]) return fail(e, FWA_E_ARG, "missing value column");
+        vals[s.col] = val_cols[s.col];
+        width[s.col] = std::max(width[s.col], dist_in_width(s.kind));
+    }
+    for (int c = 0; c < FWA_MAX_COLS; ++c) if (null_cols && ((u.nullable_cols >> c) & 1)) nulls[c] = null_cols[c];
+    if (!device) {
+        size_t need = 2 * ((((size_t)n * 8) + 255) & ~(size_t)255);
+        for (int c = 0; c < FWA_MAX_COLS; ++c) {
+            if (vals[c]) need += ((size_t)n * width[c] + 255) & ~(size_t)255;
+            if (nulls[c]) need += ((size_t)n + 255) & ~(size_t)255;
+        }
+        if (need > P->stage_bytes) {
+            if (P->d_stage) HIPCHK(e, hipFree(P->d_stage));
+            P->d_stage = nullptr;
+            P->stage_bytes = 0;
+            HIPCHK(e, hipMalloc(&P->d_stage, need));
+            P->stage_bytes = need;
+        }
+        char* p = P->d_stage;
+        hipError_t err = hipSuccess;
+        auto put = [&](const void* src, size_t bytes) -> const void* {
+            void* dst = p;
+            const hipError_t r = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, e->stream);
+            if (r != hipSuccess) err = r;
+            p += (bytes + 255) & ~(size_t)255;
+            return dst;
+        };
+        *keys = (const int64_t*)put(*keys, (size_t)n * 8);
+        *ts = (const int64_t*)put(*ts, (size_t)n * 8);
+        for (int c = 0; c < FWA_MAX_COLS; ++c) {
+            if (vals[c]) vals[c] = put(vals[c], (size_t)n * width[c]);
+            if (nulls[c]) nulls[c] = (const uint8_t*)put(nulls[c], (size_t)n);
+        }
+        HIPCHK(e, err);
+    }
+    if (n > P->mark_cap) {
+        if (P->d_mark) HIPCHK(e, hipFree(P->d_mark));
+        P->d_mark = nullptr;
+        P->mark_cap = 0;
+        const int64_t cap = std::max<int64_t>(n, 1 << 16);
+        HIPCHK(e, hipMalloc(&P->d_mark, sizeof(unsigned long long) * (size_t)cap * (size_t)P->nd));
+        P->mark_cap = cap;
+    }
+    if (int rc = dist_reserve(e, n * P->nd)) return rc;
+    DistMarkArgs a;
+    memset(&a, 0, sizeof(a));
+    a.keys = *keys;
+    a.ts = *ts;
+    a.nd = P->nd;
+    a.n = n;
+    a.q_min = dist_qmin(e);
+    a.tab = P->d_tab;
+    a.smask = (uint64_t)P->slots - 1;
+    a.ctr = P->d_ctr;
+    for (int d = 0; d < P->nd; ++d) {
+        a.src[d] = (const int64_t*)vals[P->src[d]];
+        a.nul[d] = nulls[P->src[d]];
+        a.mark[d] = P->d_mark + (size_t)d * (size_t)P->mark_cap;
+    }
+    HIPCHK(e, hipMemsetAsync(P->d_ctr + 2, 0, 8, e->stream));
+    HIPCHK(e, hipEventRecord(P->ev[0], e->stream));
+    distinct_mark_kernel<<<grid_for(n, 1 << 16), 256, 0, e->stream>>>(a, e->d_ec);
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, hipEventRecord(P->ev[1], e->stream));
+    P->timing = true;
+    HIPCHK(e, hipMemcpyAsync(P->h_ctr + 2, P->d_ctr + 2, 8, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipEventRecord(P->ev[2], e->stream));
+    P->last_add = n * P->nd;
+    // the internal layout: a source column that only COUNT(DISTINCT) read is not passed on (its index may now hold
+    // its marked column, or a DECIMAL piece); NULL flags only where the internal configuration still declares them
+    for (int d = 0; d < P->nd; ++d) {
+        bool other = false;
+        for (int j = 0; j < u.num_aggs; ++j)
+            other |= u.aggs[j].kind != FWA_COUNT && u.aggs[j].kind != FWA_COUNT_DISTINCT && u.aggs[j].col == P->src[d];
+        if (!other) vals[P->src[d]] = nullptr;
+    }
+    for (int d = 0; d < P->nd; ++d) vals[P->mcol[d]] = a.mark[d];
+    for (int c = 0; c < FWA_MAX_COLS; ++c) if (!((e->cfg.nullable_cols >> c) & 1)) nulls[c] = nullptr;
+    return FWA_OK;
+}
+
+// ---- engine snapshot / restore: the set's live entries as a section behind the FWASNAP1 body ----
+// off[max_parallelism + 1], then key[m], value[m], slice_start[m], column[m] (the marked column's ordinal: the
+// distinct source columns in first-use order), bucketed by key group like the body.
+int dist_snapshot_section(fwa_engine* e, std::vector<int64_t>* sec, int64_t* m_out) {
+    DistinctPlan* P = e->dist;
+    const int maxp = e->cfg.max_parallelism;
+    // the live entries come out of an in-place rebuild (its side buffer keeps them): the copy to the host and the
+    // host's memory are bounded by the live count, not by the table
+    int64_t m = 0;
+    std::vector<unsigned long long> w;
+    if (P->d_tab) {
+        if (int rc = dist_counters(e)) return rc;
+        const int64_t q_min = dist_qmin(e);
+        const int grid = grid_for(P->slots, kDistScanGrid);
+        if (int rc = dist_count_live(e, q_min, grid, &m)) return rc;
+        if (int rc = dist_compact(e, q_min, grid, m)) return rc;
+        P->bound = m;                                     // exact now: the pending estimate of the last push is void
+        P->last_add = 0;
+        w.resize(3 * (size_t)m);
+        for (int c = 0; c < 3 && m > 0; ++c)
+            HIPCHK(e, hipMemcpy(w.data() + (size_t)c * m, P->d_side + (size_t)c * P->side_cap, 8 * (size_t)m,
+                                hipMemcpyDeviceToHost));
+    }
+    std::vector<int32_t> kg((size_t)m);
+    std::vector<int64_t> off((size_t)maxp + 1, 0);
+    for (int64_t i = 0; i < m; ++i) {
+        const uint64_t t = w[2 * m + i];
+        const int64_t key = (t & 8) ? 0 : (int64_t)w[i];
+        kg[i] = jm::key_group_of(key, e->cfg.key_kind, 0, maxp);
+        if (kg[i] < 0) return fail(e, FWA_E_STATE, "COUNT(DISTINCT) set holds a key outside every key group");
+        off[kg[i] + 1]++;
+    }
+    for (int g = 0; g < maxp; ++g) off[g + 1] += off[g];
+    sec->assign((size_t)maxp + 1 + 4 * (size_t)m, 0);
+    memcpy(sec->data(), off.data(), 8 * ((size_t)maxp + 1));
+    int64_t* body = sec->data() + maxp + 1;
+    std::vector<int64_t> cur(off.begin(), off.end() - 1);
+    for (int64_t i = 0; i < m; ++i) {
+        const int64_t d = cur[kg[i]]++;
+        const uint64_t t = w[2 * m + i];
+        body[d] = (t & 8) ? 0 : (int64_t)w[i];
+        body[m + d] = (t & 16) ? 0 : (int64_t)w[m + i];
+        body[2 * m + d] = slice_start(e, dist_tag_q(t));
+        body[3 * m + d] = (int64_t)(t & 7);
+    }
+    *m_out = m;
+    return FWA_OK;
+}
+
+// Insert the entries of this handle's key groups from one blob's section (no marking).
+int dist_restore_section(fwa_engine* e, const int64_t* sec, int64_t m) {
+    DistinctPlan* P = e->dist;
+    const int maxp = e->cfg.max_parallelism;
+    const int64_t lo = sec[e->cfg.kg_start], hi = sec[e->cfg.kg_end + 1];
+    if (lo < 0 || hi < lo || hi > m) return fail(e, FWA_E_ARG, "corrupt COUNT(DISTINCT) key-group offsets");
+    const int64_t n = hi - lo;
+    if (n == 0) return FWA_OK;
+    const int64_t* body = sec + maxp + 1;
+    std::vector<unsigned long long> w(3 * (size_t)n);
+    for (int64_t i = 0; i < n; ++i) {
+        const uint64_t key = (uint64_t)body[lo + i], val = (uint64_t)body[m + lo + i];
+        const int64_t d = body[3 * m + lo + i];
+        if (d < 0 || d >= P->nd) return fail(e, FWA_E_ARG, "corrupt COUNT(DISTINCT) entry");
+        w[i] = key ? key : 1ull;
+        w[n + i] = val ? val : 1ull;
+        w[2 * n + i] = dist_tag(slice_q(e, body[2 * m + lo + i]), key, val, (int)d);
+    }
+    if (int rc = dist_reserve(e, n)) return rc;
+    unsigned long long* dw = nullptr;
+    HIPCHK(e, hipMalloc(&dw, 24 * (size_t)n));
+    hipError_t r = hipMemcpyAsync(dw, w.data(), 24 * (size_t)n, hipMemcpyHostToDevice, e->stream);
+    if (r == hipSuccess) {
+        distinct_insert_side_kernel<<<grid_for(n), 256, 0, e->stream>>>(dw, n, n, P->d_tab, (uint64_t)P->slots - 1, P->d_ctr);
+        r = hipGetLastError();
+    }
+    const hipError_t rs = hipStreamSynchronize(e->stream);
+    (void)hipFree(dw);
+    if (r != hipSuccess || rs != hipSuccess) return fail(e, FWA_E_DEVICE, "COUNT(DISTINCT) restore failed");
+    return FWA_OK;
+}
+
+}  // namespace

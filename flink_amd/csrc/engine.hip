@@ -2144,10 +2144,12 @@ int64_t gcd64(int64_t a, int64_t b) {
 
 struct SpState;                       // record-list window state (sparse.inc)
 struct DecPlan;                       // DECIMAL aggregates over 32-bit piece sums (decimal.inc)
+struct DistinctPlan;                  // COUNT(DISTINCT) over a marked 0/1 column and a device-resident set (distinct.inc)
 
 struct fwa_engine {
     fwa_config cfg;                   // the engine's configuration (DECIMAL handles: the internal one, see decimal.inc)
     DecPlan* dec = nullptr;
+    DistinctPlan* dist = nullptr;     // COUNT(DISTINCT) handles: cfg is the internal configuration too (distinct.inc)
     const void* dev_override[FWA_MAX_COLS] = {};   // stage_inputs: value columns already on the device
     bool restoring = false;           // fwa_restore feeding fwa_push_partials
     // FWA_KEY_PREHASHED: the caller's key.hashCode() of every key, by kid (the key table's slot), so a snapshot can
@@ -2811,6 +2813,7 @@ int reset_push_status(fwa_engine* e, bool v2bufs = false, const RelTab* tab = nu
 
 #include "sparse.inc"
 #include "decimal.inc"
+#include "distinct.inc"
 static const uint64_t kSnapMagic = 0x3150414E53415746ull;   // "FWASNAP1"
 enum { kSnapHdr = 32 };                                       // header words
 #include "reduce.inc"
@@ -2822,12 +2825,16 @@ extern "C" {
 
 const char* fwa_version(void) { return "flink_amd 0.1 (gfx950)"; }
 
-const char* fwa_last_error(const fwa_engine* e) { return e ? e->err.c_str() : "null engine"; }
+// (a NULL handle: why this thread's last fwa_create refused its configuration, where it gave a reason)
+static thread_local std::string g_create_err;
+const char* fwa_last_error(const fwa_engine* e) {
+    return e ? e->err.c_str() : (g_create_err.empty() ? "null engine" : g_create_err.c_str());
+}
 
 // internal accessors for the host-only layers compiled into the same library (heap_snapshot.cpp)
 int fwa_get_config(const fwa_engine* e, fwa_config* out) {
     if (!e || !out) return FWA_E_ARG;
-    *out = e->dec ? e->dec->ucfg : e->cfg;
+    *out = e->dist ? e->dist->ucfg : e->dec ? e->dec->ucfg : e->cfg;
     if (e->sparse) out->flags |= FWA_CFG_RECORD_LISTS;   // reports the auto-selected mode too
     out->tz = e->tz.empty() ? nullptr : e->tz.data();    // the handle's own copy (valid while it lives)
     return FWA_OK;
@@ -2856,6 +2863,7 @@ void fwa_destroy(fwa_engine* e) {
     if (e->stream) (void)hipStreamSynchronize(e->stream);
     sp_destroy(e);
     dec_free(e->dec);
+    dist_free(e->dist);
     for (int c = 0; c < 3 + FWA_MAX_AGGS; ++c) if (e->lr_col[c]) (void)hipFree(e->lr_col[c]);
     if (e->d_late) (void)hipFree(e->d_late);
     if (e->d_lr_n) (void)hipFree(e->d_lr_n);
@@ -2895,19 +2903,32 @@ int fwa_create(const fwa_config* ucfg, fwa_engine** out) {
     fwa_config uc;                               // a version-3 caller's struct ends before dec_scale
     memset(&uc, 0, sizeof(uc));
     memcpy(&uc, ucfg, ucfg->abi_version == 3 ? offsetof(fwa_config, dec_scale) : sizeof(fwa_config));
-    const int v = validate(&uc);
-    if (v) return v;
+    g_create_err.clear();
+    // COUNT(DISTINCT) -> SUM(BIGINT) of a marked column (distinct.inc), before the DECIMAL plan so the two compose
+    DistinctPlan* D = nullptr;
+    if (has_distinct(&uc)) {
+        D = new DistinctPlan();
+        fwa_config ic;
+        const int rd = dist_plan(&uc, D, &ic, &g_create_err);
+        if (rd) { delete D; return rd; }
+        uc = ic;
+    }
+    int rc = validate(&uc);
     bool dec = false;
-    for (int j = 0; j < uc.num_aggs; ++j) dec |= is_dec_kind(uc.aggs[j].kind);
-    if (!dec) return create_engine(&uc, out);
-    if (uc.abi_version == 3) return FWA_E_ARG;   // no scales
-    DecPlan* P = new DecPlan();
-    fwa_config ic;
-    int rc = dec_plan(&uc, P, &ic);
-    if (!rc) rc = validate(&ic);
-    if (!rc) rc = create_engine(&ic, out);
-    if (rc) { delete P; return rc; }
+    for (int j = 0; !rc && j < uc.num_aggs; ++j) dec |= is_dec_kind(uc.aggs[j].kind);
+    DecPlan* P = nullptr;
+    if (!rc && !dec) rc = create_engine(&uc, out);
+    else if (!rc && uc.abi_version == 3) rc = FWA_E_ARG;   // no scales
+    else if (!rc) {
+        P = new DecPlan();
+        fwa_config ic;
+        rc = dec_plan(&uc, P, &ic);
+        if (!rc) rc = validate(&ic);
+        if (!rc) rc = create_engine(&ic, out);
+    }
+    if (rc) { delete P; delete D; return rc; }
     (*out)->dec = P;
+    (*out)->dist = D;
     return FWA_OK;
 }
 
@@ -4473,17 +4494,33 @@ int fwa_push_nullable(fwa_engine* e, const int64_t* keys, const int64_t* ts, con
                       const uint8_t* const* null_cols, const int32_t* key_hash, int64_t n, int32_t flags,
                       int64_t* late_dropped_out) {
     if (!e) return FWA_E_STATE;
-    if (!e->dec || n <= 0 || n > INT32_MAX || !keys || !ts)
+    if ((!e->dec && !e->dist) || n <= 0 || n > INT32_MAX || !keys || !ts)
         return push_body(e, keys, ts, val_cols, null_cols, key_hash, n, flags, late_dropped_out);
-    // DECIMAL columns -> piece columns on the GPU, then the ordinary push over the internal configuration
+    // COUNT(DISTINCT) columns -> marked columns, DECIMAL columns -> piece columns, on the GPU; then the ordinary push
+    // over the internal configuration
     HIPCHK(e, hipSetDevice(e->cfg.device));
-    if (int rc0 = settle_push(e)) return rc0;    // a pending push may still replay from the piece columns
-    const bool device = (flags & FWA_PUSH_DEVICE_PTRS) != 0;
+    if (int rc0 = settle_push(e)) return rc0;    // a pending push may still replay from the marked / piece columns
+    bool device = (flags & FWA_PUSH_DEVICE_PTRS) != 0;
     if (device) { if (int rc1 = wait_input_stream(e)) return rc1; }
+    const void* dvals[FWA_MAX_COLS];
+    const uint8_t* dnulls[FWA_MAX_COLS];
+    if (e->dist) {   // (host inputs are staged by the marking pass: a device push from here on)
+        if (int rc2 = dist_mark(e, &keys, &ts, val_cols, null_cols, n, device, dvals, dnulls)) return rc2;
+        val_cols = dvals;
+        null_cols = dnulls;
+        key_hash = nullptr;
+        device = true;
+        flags |= FWA_PUSH_DEVICE_PTRS;
+    }
     const void* vals[FWA_MAX_COLS];
-    int rc = dec_split(e, val_cols, null_cols, n, device, vals);
-    if (!rc) rc = push_body(e, keys, ts, vals, null_cols, key_hash, n, flags, late_dropped_out);
+    int rc = FWA_OK;
+    if (e->dec) {
+        rc = dec_split(e, val_cols, null_cols, n, device, vals);
+        val_cols = vals;
+    }
+    if (!rc) rc = push_body(e, keys, ts, val_cols, null_cols, key_hash, n, flags, late_dropped_out);
     for (int c = 0; c < FWA_MAX_COLS; ++c) e->dev_override[c] = nullptr;
+    dist_collect_timing(e);
     return rc;
 }
 
@@ -4593,6 +4630,7 @@ int fwa_push_partials(fwa_engine* e, const int64_t* keys, const int64_t* slice_t
                       const void* const* acc, int64_t n, int32_t flags, int64_t* late_dropped_out) {
     if (!e) return FWA_E_STATE;
     if (e->dec && !e->restoring) return fail(e, FWA_E_UNSUPPORTED, "partial accumulators of DECIMAL aggregates");
+    if (e->dist && !e->restoring) return fail(e, FWA_E_UNSUPPORTED, kDistNoPartials);
     if (e->red) return fail(e, FWA_E_UNSUPPORTED, "partial accumulators of a DataStream reduction");
     if (e->kind == FWA_SESSION) return fail(e, FWA_E_UNSUPPORTED, "partial accumulators need a slicing window");
     if (n < 0 || (n > 0 && (!keys || !slice_ts || !count))) return fail(e, FWA_E_ARG, "null input column");
@@ -4746,6 +4784,7 @@ int fwa_drain_route(fwa_engine* e, int64_t wm, int32_t parallelism, fwa_routed* 
     if (!e || !out) return FWA_E_ARG;
     memset(out, 0, sizeof(*out));
     if (parallelism < 1 || parallelism > FWA_MAX_DEST) return fail(e, FWA_E_ARG, "fwa_drain_route: parallelism");
+    if (e->dist) return fail(e, FWA_E_UNSUPPORTED, kDistNoPartials);
     if (e->red || e->dec || e->kind == FWA_SESSION || e->sparse || !e->cfg.output_on_device ||
         e->cfg.key_kind == FWA_KEY_PREHASHED)
         return fail(e, FWA_E_UNSUPPORTED, "fwa_drain_route: a dense slicing-window handle with output_on_device");
@@ -4848,6 +4887,7 @@ int fwa_fire_partials(fwa_engine* e, const int64_t* rows, int64_t n, int32_t m, 
     if (!e) return FWA_E_STATE;
     if (out) memset(out, 0, sizeof(*out));
     if (late_dropped_out) *late_dropped_out = 0;
+    if (e->dist) return fail(e, FWA_E_UNSUPPORTED, kDistNoPartials);
     const int na = e->ec.naggs;
     if (n < 0 || m < 3 || m > 3 + kMaxAggsInt || (n > 0 && !rows) || !acc_cell)
         return fail(e, FWA_E_ARG, "fwa_fire_partials: rows / cells");
@@ -5009,6 +5049,7 @@ int fwa_drain_partials(fwa_engine* e, int64_t wm, fwa_partials* out) {
     e->rs_valid = false;                              // the drained slices leave the carried sums behind
     if (e->red) return fail(e, FWA_E_UNSUPPORTED, "partial accumulators of a DataStream reduction");
     if (e->dec) return fail(e, FWA_E_UNSUPPORTED, "partial accumulators of DECIMAL aggregates");
+    if (e->dist) return fail(e, FWA_E_UNSUPPORTED, kDistNoPartials);
     if (e->kind == FWA_SESSION) return fail(e, FWA_E_UNSUPPORTED, "partial accumulators need a slicing window");
     HIPCHK(e, hipSetDevice(e->cfg.device));
     if (int rc0 = settle_pending(e)) return rc0;
@@ -5084,7 +5125,9 @@ int fwa_drain_partials(fwa_engine* e, int64_t wm, fwa_partials* out) {
 // header word layout: 0 magic, 1 version, 2 window kind, 3 semantics, 4 size, 5 slide, 6 offset, 7 gap,
 // 8 allowed lateness, 9 max parallelism, 10 key kind, 11 num aggs, 12..19 agg kinds, 20 watermark,
 // 21 entries, 22 kg_start, 23 kg_end of the snapshotting handle, 24 nullable_cols, 25 hidden non-NULL
-// counters (columns after the acc_j columns), 26 aggregate input columns (4 bits each), 27..31 reserved (0)
+// counters (columns after the acc_j columns), 26 aggregate input columns (4 bits each), 27 the bitmask of the
+// caller's COUNT(DISTINCT) aggregates, 28 the entries of their set's section behind the body (both 0 for other
+// handles, distinct.inc), 29..31 reserved (0)
 
 static void snap_header(const fwa_engine* e, int64_t* h, int64_t n) {
     memset(h, 0, sizeof(int64_t) * kSnapHdr);
@@ -5108,6 +5151,7 @@ static void snap_header(const fwa_engine* e, int64_t* h, int64_t n) {
     h[24] = e->cfg.nullable_cols;
     h[25] = e->ec.naggs - e->ec.nout;
     for (int j = 0; j < e->cfg.num_aggs; ++j) h[26] |= (int64_t)(e->cfg.aggs[j].col & 15) << (4 * j);
+    h[27] = e->dist ? e->dist->mask : 0;   // the caller's aggregates that are COUNT(DISTINCT); h[28]: their set's entries
 }
 
 // Sessions: the blob's entries are the in-flight sessions (key, start, count, acc_j..., end) bucketed by
@@ -5325,10 +5369,15 @@ int fwa_snapshot(fwa_engine* e, fwa_blob* out) {
         off[kg[i] + 1]++;
     }
     for (int g = 0; g < maxp; ++g) off[g + 1] += off[g];
-    const size_t words = kSnapHdr + (size_t)maxp + 1 + (size_t)n * ncb;
+    std::vector<int64_t> dsec;                         // COUNT(DISTINCT): the set's live entries behind the body
+    int64_t dm = 0;
+    if (e->dist) { if (int rc = dist_snapshot_section(e, &dsec, &dm)) return rc; }
+    const size_t words0 = kSnapHdr + (size_t)maxp + 1 + (size_t)n * ncb, words = words0 + dsec.size();
     int64_t* b = (int64_t*)malloc(words * 8);
     if (!b) return fail(e, FWA_E_OOM, "snapshot blob allocation failed");
     snap_header(e, b, n);
+    b[28] = dm;
+    if (!dsec.empty()) memcpy(b + words0, dsec.data(), 8 * dsec.size());
     memcpy(b + kSnapHdr, off.data(), 8 * ((size_t)maxp + 1));
     int64_t* body = b + kSnapHdr + maxp + 1;
     std::vector<int64_t> cur(off.begin(), off.end() - 1);
@@ -5370,8 +5419,11 @@ int fwa_restore(fwa_engine* e, const void* const* blobs, const int64_t* sizes, i
             if (h[w] != ref[w]) return fail(e, FWA_E_ARG, "snapshot window/aggregate configuration differs");
         for (int w = 24; w < 27; ++w)
             if (h[w] != ref[w]) return fail(e, FWA_E_ARG, "snapshot nullable-column configuration differs");
-        const int64_t n = h[21];
-        if (n < 0 || sizes[b] != (int64_t)(8 * (kSnapHdr + maxp + 1 + (size_t)n * ncols)))
+        if (h[27] != ref[27]) return fail(e, FWA_E_ARG, "snapshot COUNT(DISTINCT) aggregates differ");
+        const int64_t n = h[21], dm = h[28];
+        const size_t dwords = e->dist ? (size_t)maxp + 1 + 4 * (size_t)std::max<int64_t>(dm, 0) : 0;
+        if (n < 0 || dm < 0 || (!e->dist && dm) ||
+            sizes[b] != (int64_t)(8 * (kSnapHdr + maxp + 1 + (size_t)n * ncols + dwords)))
             return fail(e, FWA_E_ARG, "snapshot size does not match its entry count");
     }
     if (e->kind == FWA_SESSION) return restore_sessions(e, blobs, n_blobs);
@@ -5386,6 +5438,9 @@ int fwa_restore(fwa_engine* e, const void* const* blobs, const int64_t* sizes, i
         const int64_t* off = h + kSnapHdr;
         const int64_t lo = off[e->cfg.kg_start], hi = off[e->cfg.kg_end + 1];
         if (lo < 0 || hi < lo || hi > n) return fail(e, FWA_E_ARG, "corrupt key-group offsets");
+        if (e->dist) {   // the set's entries of this handle's key groups (not marked: their records were counted)
+            if (int rc = dist_restore_section(e, off + maxp + 1 + (size_t)n * ncols, h[28])) return rc;
+        }
         if (hi == lo) continue;
         const int64_t* body = off + maxp + 1;
         const void* acc[FWA_MAX_AGGS + FWA_MAX_COLS] = {};
@@ -5831,6 +5886,7 @@ int fwa_get_stats(fwa_engine* e, fwa_stats* s) {
     s->live_keys = (int64_t)e->h_st->n_keys;
     s->live_slices = e->kind == FWA_SESSION ? e->n_ss : e->sparse ? sp_live_windows(e) : (int64_t)e->live.size();
     s->current_watermark = e->wm;
+    dist_collect_timing(e);                  // (a COUNT(DISTINCT) marking pass not yet added to ingest_ms)
     s->ingest_launches = e->ingest_launches;
     s->ingest_ms = e->ingest_ms;
     s->ingest_records = e->ingest_records;
@@ -5857,6 +5913,7 @@ int fwa_reset_timers(fwa_engine* e) {
     if (!e) return FWA_E_ARG;
     if (int rc0 = settle_pending(e)) return rc0;
     e->ingest_launches = e->ingest_records = e->replay_records = e->fire_launches = e->fire_rows = 0;
+    dist_collect_timing(e);
     e->ingest_ms = e->fire_ms = e->partition_ms = e->combine_ms = 0;
     return FWA_OK;
 }
@@ -5878,6 +5935,15 @@ int fwa_set_option(fwa_engine* e, int32_t option, int64_t value) {
         case FWA_OPT_SLIDE_CARRIED: e->rs_on = value != 0; e->rs_valid = false; return FWA_OK;
         case FWA_OPT_FIRE_PARTIALS: e->opt_fire_partials = value != 0 ? 1 : 0; return FWA_OK;
         case FWA_OPT_DEC_WRAP_NULL: e->opt_dec_wrap_null = value != 0 ? 1 : 0; return FWA_OK;
+        case FWA_OPT_DISTINCT_SLOTS:
+            if (!e->dist) return fail(e, FWA_E_UNSUPPORTED, "FWA_OPT_DISTINCT_SLOTS: no COUNT(DISTINCT) aggregate");
+            if (e->dist->d_tab) return fail(e, FWA_E_STATE, "FWA_OPT_DISTINCT_SLOTS: before the first push");
+            if (value < 64 || (value & (value - 1)) || value > ((int64_t)1 << 40))
+                return fail(e, FWA_E_ARG, "FWA_OPT_DISTINCT_SLOTS: a power of two >= 64");
+            e->dist->first_slots = value;
+            return FWA_OK;
+        case FWA_OPT_DISTINCT_LIVE: case FWA_OPT_DISTINCT_REBUILDS:
+            return fail(e, FWA_E_ARG, "read-only option");
         default: return fail(e, FWA_E_ARG, "unknown option");
     }
 }
@@ -5905,6 +5971,11 @@ int fwa_get_option(const fwa_engine* e, int32_t option, int64_t* value) {
         case FWA_OPT_DEC_WRAP_NULL: *value = e->opt_dec_wrap_null; return FWA_OK;
         case FWA_OPT_FUSED_FIRES: *value = e->fused_fires; return FWA_OK;
         case FWA_OPT_RESET_LAUNCHES: *value = e->reset_launches; return FWA_OK;
+        case FWA_OPT_DISTINCT_SLOTS: case FWA_OPT_DISTINCT_LIVE: case FWA_OPT_DISTINCT_REBUILDS:
+            if (!e->dist) return FWA_E_UNSUPPORTED;
+            *value = option == FWA_OPT_DISTINCT_SLOTS ? (e->dist->slots ? e->dist->slots : e->dist->first_slots)
+                   : option == FWA_OPT_DISTINCT_LIVE ? e->dist->live : e->dist->rebuilds;
+            return FWA_OK;
         default: return FWA_E_ARG;
     }
 }

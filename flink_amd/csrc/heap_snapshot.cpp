@@ -292,6 +292,13 @@ bool supported(const fwa_config& c, bool dict = false) {
 }
 const char* kUnsupported = "heap layout: DataStream TUMBLE / SLIDE / SESSION aggregates and Table TUMBLE / HOP / CUMULATE / "
                            "SESSION with a computable key hash";
+// COUNT(DISTINCT) handles have their own reason: the reference keeps the distinct values as MapView bytes
+const char* kNoDistinct = "heap layout of COUNT(DISTINCT): the set of values (MapView bytes in the reference) is not "
+                          "written; fwa_snapshot / fwa_restore carry it";
+const char* why_unsupported(const fwa_config& c) {
+    for (int j = 0; j < c.num_aggs; ++j) if (c.aggs[j].kind == FWA_COUNT_DISTINCT) return kNoDistinct;
+    return kUnsupported;
+}
 
 int64_t gcd64(int64_t a, int64_t b) { while (b) { const int64_t t = a % b; a = b; b = t; } return a; }
 
@@ -590,7 +597,7 @@ static int snapshot_heap_impl(fwa_engine* e, fwa_keydict* dict, fwa_blob* out, i
     fwa_config c;
     int rc = fwa_get_config(e, &c);
     if (rc) return rc;
-    if (!supported(c, dict != nullptr)) return fwa_set_error(e, FWA_E_UNSUPPORTED, kUnsupported);
+    if (!supported(c, dict != nullptr)) return fwa_set_error(e, FWA_E_UNSUPPORTED, why_unsupported(c));
     DictRows dr;
     if (dict && (rc = fwa_keydict_host_rows(dict, &dr.arity, dr.types, &dr.slots, &dr.nulls)))
         return fwa_set_error(e, rc, "key dictionary rows");
@@ -813,7 +820,7 @@ static int restore_heap_impl(fwa_engine* e, fwa_keydict* dict, const void* const
     fwa_config c;
     int rc = fwa_get_config(e, &c);
     if (rc) return rc;
-    if (!supported(c, dict != nullptr)) return fwa_set_error(e, FWA_E_UNSUPPORTED, kUnsupported);
+    if (!supported(c, dict != nullptr)) return fwa_set_error(e, FWA_E_UNSUPPORTED, why_unsupported(c));
     int32_t darity = 1;
     int32_t dtypes[FWA_KEYDICT_MAX_ARITY] = {};
     bool dstr = false;

@@ -152,7 +152,7 @@ def _check(rc, h=None, what=""):
 OPTIONS = {"skew_merge": 1, "window_passes": 2, "narrow_entries": 3, "session_cells": 4, "out_min_rows": 5,
            "partials_one_pass": 6, "sp_table": 7, "sp_fmax": 8, "sp_budget": 9, "profile": 10,
            "session_path": 11, "ingest_variant": 12, "slide_carried": 13, "fire_partials": 14, "dec_wrap_null": 15,
-           "fused_fires": 16, "reset_launches": 17}
+           "fused_fires": 16, "reset_launches": 17, "distinct_slots": 18, "distinct_live": 19, "distinct_rebuilds": 20}
 # options applied to every new handle of this process before its own (test tooling sets these, e.g.
 # tests/forced_modes_check.py); empty in production
 DEFAULT_OPTIONS = {}
@@ -168,8 +168,9 @@ class WindowAggregator:
         self._inflight = None     # inputs of an FWA_PUSH_ASYNC push, kept alive until the next call settles it
         self._in_stream = None
         rc = lib().fwa_create(C.byref(cfg), C.byref(self.h))
-        if rc:
-            raise EngineError(rc, "fwa_create")
+        if rc:                                         # (a refused configuration may say why: fwa_last_error(NULL))
+            why = lib().fwa_last_error(None).decode()
+            raise EngineError(rc, "fwa_create" + (": " + why if why and why != "null engine" else ""))
         for name, value in DEFAULT_OPTIONS.items():    # where they apply to this handle's state layout
             opt = OPTIONS[name] if name in OPTIONS else int(name)
             rc = lib().fwa_set_option(self.h, opt, int(value))

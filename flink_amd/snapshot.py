@@ -21,11 +21,13 @@ def parse(blob):
     session = int(w[2]) == 3                     # SESSION: a 4th leading column holds the session end (last)
     prehashed = int(w[10]) == 2                  # FWA_KEY_PREHASHED: a last column holds each key's key.hashCode()
     ncols = (4 if session else 3) + naggs + nh + (1 if prehashed else 0)   # nh: hidden non-NULL counters
-    need = HDR_WORDS + maxp + 1 + n * ncols
+    dmask, dm = int(w[27]), int(w[28])           # COUNT(DISTINCT): aggregate bitmask, entries of the distinct set
+    body_end = HDR_WORDS + maxp + 1 + n * ncols
+    need = body_end + (maxp + 1 + 4 * dm if dmask else 0)
     if w.size != need:
         raise ValueError("snapshot size %d words != %d" % (w.size, need))
     off = w[HDR_WORDS:HDR_WORDS + maxp + 1]
-    body = w[HDR_WORDS + maxp + 1:].reshape(ncols, n) if n else np.zeros((ncols, 0), np.int64)
+    body = w[HDR_WORDS + maxp + 1:body_end].reshape(ncols, n) if n else np.zeros((ncols, 0), np.int64)
     out = {
         "window_kind": int(w[2]), "semantics": int(w[3]), "size_ms": int(w[4]), "slide_ms": int(w[5]),
         "offset_ms": int(w[6]), "gap_ms": int(w[7]), "allowed_lateness_ms": int(w[8]),
@@ -39,6 +41,11 @@ def parse(blob):
         out["window_end"] = body[3 + naggs + nh].copy()   # slice_start holds the session start
     if prehashed:
         out["key_hash"] = body[ncols - 1].astype(np.int32)
+    if dmask:                                    # the live (key, value, slice, column) entries behind the body
+        sec = w[body_end + maxp + 1:].reshape(4, dm) if dm else np.zeros((4, 0), np.int64)
+        out["distinct"] = {"agg_mask": dmask, "n": dm, "kg_offsets": w[body_end:body_end + maxp + 1].copy(),
+                           "key": sec[0].copy(), "value": sec[1].copy(), "slice_start": sec[2].copy(),
+                           "column": sec[3].copy()}
     return out
 
 

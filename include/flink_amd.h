@@ -115,8 +115,39 @@ enum fwa_agg_kind {
     FWA_MAXBY_F32 = 30,
     FWA_SEL_64 = 31,   /* 8-byte field of the element minBy / maxBy selected                [i64 bits] */
     FWA_SEL_32 = 32,   /* 4-byte field of the element minBy / maxBy selected                [i32 bits] */
-    FWA_AGG_KIND_COUNT = 33
+    FWA_COUNT_DISTINCT = 33,/* COUNT(DISTINCT col) over an 8-byte value column compared by its 64 bits (below) [i64] */
+    FWA_AGG_KIND_COUNT = 34
 };
+/* COUNT(DISTINCT col) (FWA_COUNT_DISTINCT; the distinct view of the planner's AggsHandleFunction, DistinctInfo): the
+ * number of different non-NULL values of col among the window's accepted records. col is an 8-byte column and two
+ * values are equal iff their 64 bits are: the caller maps other SQL types to 64 bits itself -- INT sign-extended,
+ * DOUBLE by its bits (normalise -0.0 / NaN first if SQL equality is wanted), STRING / VARCHAR values as the ids of a
+ * one-field fwa_keydict (FWA_KEY_FIELD_STRING; equal strings get equal ids). The result is never NULL: a window with no
+ * non-NULL value gives 0 and fwa_out.agg_null[j] stays a NULL pointer; NULL inputs (fwa_push_nullable) are ignored.
+ * It stands beside every other Table aggregate of the handle, DECIMAL included; up to FWA_MAX_AGGS of them, two over
+ * the same column sharing their work. Internally the aggregate is SUM(BIGINT) over a 0/1 column "first record of its
+ * (key, window, value)" that a GPU pass ahead of the ingest writes from a device-resident set (flink_amd/csrc/
+ * distinct.inc); the set's memory is bounded by the entries of the windows that have not fired plus one batch.
+ * Accepted: FWA_TUMBLE with FWA_SEM_TABLE, size_ms >= 64 (the set keeps 58 bits of the window number), key kinds
+ * JAVA_LONG, BINROW_BIGINT and GROUP_PREFIXED, any offset, a shift time zone, nullable columns, FWA_CFG_LATE_INDICES,
+ * FWA_CFG_RECORD_LISTS (forced or auto-selected). FWA_E_UNSUPPORTED (fwa_last_error names COUNT(DISTINCT); for a
+ * refused fwa_create, fwa_last_error(NULL) on the calling thread):
+ *   FWA_SLIDE, FWA_CUMULATE, FWA_SESSION -- a window of several slices needs the union of the per-slice sets, which is
+ *     not additive;
+ *   FWA_SEM_DATASTREAM, FWA_CFG_REDUCE, FWA_KEY_PREHASHED -- the engine snapshot needs each entry's key group and no
+ *     hash is kept per set entry;
+ *   fwa_drain_partials, fwa_push_partials, fwa_drain_route, fwa_fire_partials -- a distinct count is not mergeable
+ *     without shipping the sets;
+ *   fwa_snapshot_heap* / fwa_restore_heap* -- the reference keeps the values as MapView bytes.
+ * fwa_snapshot / fwa_restore carry the set (the blob layout below); fwa_get_config returns the caller's configuration.
+ * Needs one value-column index that no other aggregate uses per distinct column that another aggregate also reads
+ * (FWA_E_UNSUPPORTED when none of the FWA_MAX_COLS is free).
+ * A push that fails after its marking pass ran (FWA_E_KEYGROUP, FWA_E_TS_MIN, a device error: they are found by the
+ * ingest, behind the pass) leaves its values in the set: the batch pushed again would find them there and count
+ * them 0 times. Like the reference operator after an exception in processElement, such a handle is to be destroyed
+ * and restored from its last snapshot, not retried.
+ * size_ms >= 64 is a deliberate limit of this build: a smaller slice number could be kept whole only by a fourth
+ * CAS word per entry or by a host check of every push's slice range; the 64 ms bound costs neither. */
 /* Built-in DataStream reductions (FWA_CFG_REDUCE): WindowedStream.sum / min / max / minBy / maxBy(pos)
  * (WindowedStream.java:680-890) reduce the window's elements in arrival order with SumAggregator
  * (SumAggregator.java:66-76) or ComparableAggregator (ComparableAggregator.java:83-107): the result is a copy of the
@@ -268,7 +299,7 @@ typedef struct fwa_stats {
     int64_t current_watermark;
     /* device time of the engine's kernels, measured with HIP events on the handle's stream */
     int64_t ingest_launches;
-    double ingest_ms;            /* sum over ingest-kernel launches */
+    double ingest_ms;            /* sum over ingest-kernel launches, and over the marking passes of COUNT(DISTINCT) handles */
     int64_t ingest_records;      /* distinct records pushed through those launches (replays excluded) */
     int64_t fire_launches;
     double fire_ms;
@@ -432,7 +463,13 @@ int fwa_fire_partials(fwa_engine* e, const int64_t* rows, int64_t n, int32_t m, 
  * acc_j columns. FWA_KEY_PREHASHED handles (keys of any Java type as 64-bit ids beside their key.hashCode()): one
  * more last column hash[n], the hashCode() each key was pushed with (the engine keeps it per key), by which the
  * entries are placed in key groups and a restore places them again; record-list handles keep no per-key hash and
- * refuse (FWA_E_UNSUPPORTED). The blob is engine-allocated; free it with fwa_blob_free. */
+ * refuse (FWA_E_UNSUPPORTED). COUNT(DISTINCT) handles (header word 27 = the bitmask of the caller's aggregates that are
+ * FWA_COUNT_DISTINCT, compared by fwa_restore; 0 and no section otherwise, so other blobs are unchanged): behind the
+ * body, the live entries of the distinct set -- a second key-group offset table doff[max_parallelism + 1], then SoA
+ * columns key[m], value[m], slice_start[m], column[m] (the ordinal of the entry's distinct source column, in
+ * first-use order of the aggregate list), m = header word 28; the counts themselves travel as the acc_j sums of the
+ * body. A restore inserts the entries of its own key groups, so values seen before the checkpoint are not counted
+ * again. The blob is engine-allocated; free it with fwa_blob_free. */
 typedef struct fwa_blob {
     void* data;
     int64_t size;   /* bytes */
@@ -534,7 +571,13 @@ enum fwa_option {
                                   * (FWA_E_UNSUPPORTED) instead of a silently different result */
     FWA_OPT_FUSED_FIRES = 16,    /* read only: watermark fires that restored the identities of the slots they retired in
                                     the same pass (fwa_get_option) */
-    FWA_OPT_RESET_LAUNCHES = 17  /* read only: launches of the separate slot-reset kernel (fwa_get_option) */
+    FWA_OPT_RESET_LAUNCHES = 17, /* read only: launches of the separate slot-reset kernel (fwa_get_option) */
+    FWA_OPT_DISTINCT_SLOTS = 18, /* COUNT(DISTINCT): first size of the set in slots (a power of two >= 64, before the
+                                    first push; default: sized from the first push); tests force growth with it.
+                                    fwa_get_option: the current size */
+    FWA_OPT_DISTINCT_LIVE = 19,  /* read only: set entries of unfired windows counted at the last rebuild */
+    FWA_OPT_DISTINCT_REBUILDS = 20 /* read only: rebuilds of the set (growth, dropping fired windows' entries, and one
+                                      per fwa_snapshot, which reads the live entries out of a rebuild) */
 };
 int fwa_set_option(fwa_engine* e, int32_t option, int64_t value);
 /* The option's effective value: for the tri-state options 1 if the handle currently takes that path (forced, or
