@@ -2331,6 +2331,7 @@ struct fwa_engine {
     // per-handle options (fwa_set_option; the defaults are the production behaviour)
     int32_t opt_pre = -1, opt_mp = -1, opt_narrow = -1, opt_cells = -1;   // -1 adaptive, 0 never, 1 always
     int32_t opt_variant = 0;                                              // FWA_OPT_INGEST_VARIANT (A/B builds)
+    int64_t stragglers = 0;                                               // FWA_OPT_STRAGGLERS
     bool rows_zero = false;             // d_st->rows is 0: push_reset_kernel ran and nothing has fired since
     int64_t fused_fires = 0;            // fires that also retired their slots (FWA_OPT_FUSED_FIRES)
     int64_t reset_launches = 0;         // reset_slots_kernel launches (FWA_OPT_RESET_LAUNCHES)
@@ -3540,7 +3541,7 @@ static int push_v2(fwa_engine* e, IngestArgs& a, bool* ran) {
     const size_t lds3 = seg3 * 8 + 2 * seg3 * 4 + (size_t)(e->nacc_comb - 1) * 2 * seg3 * 8 + 4 * 4 * kSub + 16;
     // entries per lane and chunk: the largest counts whose kernels keep every value in registers at 1024 threads (a VGPR
     // spill is not harmless here, DESIGN.md section 4 "Skewed keys"; tests/test_abi.py checks the code object): 4, 3 with
-    // two carried value columns, 6 for narrow entries, 2 with window passes. 512-thread blocks with twice the entries are
+    // two carried value columns, 6 for narrow entries (the lean body too: 8 spill), 2 with window passes. 512-thread blocks with twice the entries are
     // spill-free too but slower (r05 A/B, profiles/r05_combine_geometry_ab.txt). -D switches for A/B builds only.
 #ifndef FWA_C3_TH
 #define FWA_C3_TH 1024
@@ -3571,7 +3572,10 @@ static int push_v2(fwa_engine* e, IngestArgs& a, bool* ran) {
         else C3M(IT, NV, 0, 0); } while (0)
     if (narrow) {   // packed entries free the prefetch registers: more entries per lane and chunk
         if (mp) combine3_kernel<FWA_MP_IT, 2, 1, TH3, 1, 0, 1, 1><<<e->np, TH3, lds3, e->stream>>>(ca, e->d_ec);
-        else combine3_kernel<FWA_C3_NIT, 2, 1, TH3, 1, 0, 0, 1><<<e->np, TH3, lds3, e->stream>>>(ca, e->d_ec);
+        // the lean body (ingest.inc: 4-byte key image in LDS, first probes in batches of 3, misses deferred); variant
+        // bit 1: the general body on the same entries (A/B)
+        else if (TH3 != 1024 || (e->opt_variant & 2)) combine3_kernel<FWA_C3_NIT, 2, 1, TH3, 1, 0, 0, 1><<<e->np, TH3, lds3, e->stream>>>(ca, e->d_ec);
+        else combine3_kernel<6, 2, 1, 1024, 1, 0, 0, 1, 3><<<e->np, 1024, lds3, e->stream>>>(ca, e->d_ec);
     } else if (narrow2) {
         if (mp) combine3_kernel<FWA_MP_IT, 2, 2, TH3, 0, 0, 1, 2><<<e->np, TH3, lds3, e->stream>>>(ca, e->d_ec);
         else combine3_kernel<4, 2, 2, TH3, 0, 0, 0, 2><<<e->np, TH3, lds3, e->stream>>>(ca, e->d_ec);
@@ -4417,6 +4421,7 @@ static int push_settle(fwa_engine* e, IngestArgs& a, int64_t n, bool ran_v2, boo
         const DevStatus st = *e->h_st;
         if (ran_v2 && round == 0 && (int64_t)st.ovf_n * 64 > n) e->pre = true;   // skewed keys: PRE from the next push
         if (ran_v2 && round == 0 && (int64_t)st.strag_n * 64 > n) e->mp = true;  // wide chunks: window passes
+        if (ran_v2 && round == 0) e->stragglers += st.strag_n;
         if (ran_v2 && round == 0 && e->narrow_used && (int64_t)st.wide_n * 64 > n) e->narrow = false;   // 64-bit keys / values
         if (st.error) {
             const char* m = st.error == FWA_E_KEYGROUP ? "Key group is not in the owned KeyGroupRange (StateTable.getMapForKeyGroup)"
@@ -5942,7 +5947,7 @@ int fwa_set_option(fwa_engine* e, int32_t option, int64_t value) {
                 return fail(e, FWA_E_ARG, "FWA_OPT_DISTINCT_SLOTS: a power of two >= 64");
             e->dist->first_slots = value;
             return FWA_OK;
-        case FWA_OPT_DISTINCT_LIVE: case FWA_OPT_DISTINCT_REBUILDS:
+        case FWA_OPT_DISTINCT_LIVE: case FWA_OPT_DISTINCT_REBUILDS: case FWA_OPT_STRAGGLERS: case FWA_OPT_KEY_TABLE_DIGEST:
             return fail(e, FWA_E_ARG, "read-only option");
         default: return fail(e, FWA_E_ARG, "unknown option");
     }
@@ -5971,6 +5976,17 @@ int fwa_get_option(const fwa_engine* e, int32_t option, int64_t* value) {
         case FWA_OPT_DEC_WRAP_NULL: *value = e->opt_dec_wrap_null; return FWA_OK;
         case FWA_OPT_FUSED_FIRES: *value = e->fused_fires; return FWA_OK;
         case FWA_OPT_RESET_LAUNCHES: *value = e->reset_launches; return FWA_OK;
+        case FWA_OPT_STRAGGLERS: *value = e->stragglers; return FWA_OK;
+        case FWA_OPT_KEY_TABLE_DIGEST: {   // FNV-1a over the table's words in slot order (the side slot included)
+            std::vector<unsigned long long> table((size_t)e->capacity + 1);
+            if (!e->d_keys || hipStreamSynchronize(e->stream) != hipSuccess ||
+                hipMemcpy(table.data(), e->d_keys, 8 * table.size(), hipMemcpyDeviceToHost) != hipSuccess) return FWA_E_DEVICE;
+            uint64_t h = 0xcbf29ce484222325ull;
+            for (unsigned long long w : table)
+                for (int b = 0; b < 8; ++b) h = (h ^ ((w >> (8 * b)) & 0xff)) * 0x100000001b3ull;
+            *value = (int64_t)h;
+            return FWA_OK;
+        }
         case FWA_OPT_DISTINCT_SLOTS: case FWA_OPT_DISTINCT_LIVE: case FWA_OPT_DISTINCT_REBUILDS:
             if (!e->dist) return FWA_E_UNSUPPORTED;
             *value = option == FWA_OPT_DISTINCT_SLOTS ? (e->dist->slots ? e->dist->slots : e->dist->first_slots)

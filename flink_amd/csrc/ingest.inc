@@ -969,14 +969,368 @@ __device__ __forceinline__ uint32_t kswz(uint32_t s) { return s ^ (((s >> 5) & 3
 typedef __attribute__((address_space(1))) unsigned long long g_u64;
 typedef const __attribute__((address_space(1))) unsigned long long* gc_u64_ptr;
 
+// ------------------------------------------------------------------------------------------------
+// combine3, lean body (DESIGN.md §5 "Lean narrow combiner"): the narrow flagship shape -- NW 1, LAYOUT 1 (COUNT + one
+// BIGINT SUM), no PRE, no MP. Same LDS accumulators, window, stragglers and errors as the general body below; what
+// differs is how a chunk's entries find their slots:
+//  * the partition's key segment is held in LDS as a 4-byte image: kLeanEmpty for kEmptyKey, the low word for a key
+//    that fits int32, kLeanForeign for any other resident (a 64-bit key of the v1 replay: occupied, never matches).
+//    partition3 sends both marker values to the v1 replay, so no entry key equals a marker. A bucket is 32 bytes:
+//    two ds_read_b128, eight 32-bit compares;
+//  * hashes and bucket addresses are computed before the chunk barrier; after it the home buckets of BT entries are
+//    read together (one exposed LDS latency per batch) and matched with a select chain: "found, and where" only;
+//  * entries not found in their home bucket set a bit in a per-lane mask; one loop per chunk takes each lane's lowest
+//    missed entry through the general probe (next buckets, first empty slot in logical order, 32-bit CAS insert);
+//  * a chunk whose entries are, for the whole wave, valid, found, inside the window and no stragglers issues its
+//    LDS adds back to back; any other chunk runs the per-entry code of the general body.
+// On exit only the slots this block filled are written to the 64-bit table (sign-extended); foreign and untouched
+// slots are never rewritten.
+constexpr int32_t kLeanEmpty = (int32_t)0x80000000;
+constexpr int32_t kLeanForeign = (int32_t)0x80000001;
+typedef int32_t lean_i4 __attribute__((ext_vector_type(4)));
+
+// The 4-byte segment is stored swizzled like the 8-byte one: the two 16-byte quads of a 32-byte bucket are exchanged by
+// the bucket index's bit 3 (logical slot s at s ^ (((s >> 6) & 1) << 2)), so the first quads of 16 random buckets fall
+// on all 16 bank groups of 16 bytes of a 256-byte LDS row (unswizzled: on the 8 even ones).
+__device__ __forceinline__ uint32_t kswz32(uint32_t s) { return s ^ (((s >> 6) & 1u) << 2); }
+
+__device__ __forceinline__ int32_t lean_key_image(unsigned long long k) {
+    if (k == kEmptyKey) return kLeanEmpty;
+    const bool narrow = (int64_t)(int32_t)(uint32_t)k == (int64_t)k && (uint32_t)k - 0x80000000u > 1u;
+    return narrow ? (int32_t)(uint32_t)k : kLeanForeign;
+}
+
+// Make the compiler have every bucket of a batch loaded HERE: one statement, so no read can sink behind another
+// entry's match (see consume()).
+template <int BT>
+__device__ __forceinline__ void lean_pin(const lean_i4* qa, const lean_i4* qb) {
+    static_assert(BT >= 1 && BT <= 4, "batch size");
+    if constexpr (BT == 1) asm volatile("" : : "v"(qa[0]), "v"(qb[0]));
+    else if constexpr (BT == 2) asm volatile("" : : "v"(qa[0]), "v"(qb[0]), "v"(qa[1]), "v"(qb[1]));
+    else if constexpr (BT == 3) asm volatile("" : : "v"(qa[0]), "v"(qb[0]), "v"(qa[1]), "v"(qb[1]), "v"(qa[2]), "v"(qb[2]));
+    else asm volatile("" : : "v"(qa[0]), "v"(qb[0]), "v"(qa[1]), "v"(qb[1]), "v"(qa[2]), "v"(qb[2]), "v"(qa[3]), "v"(qb[3]));
+}
+
+// Which of a bucket's 8 physical slots holds kk (-1: none). Eight compares into eight scalar masks, then eight selects:
+// written out because the compiler chains compare and select through VCC, with a wait slot between the two every time
+// (a VALU write of a scalar mask needs two wait states before a VALU read of it; here eight instructions lie between).
+// The selects run from slot 7 down to slot 0, each eight instructions behind its compare: the lowest matching slot wins
+// (a key is in a bucket once at most; the empty test of the general probe wants the first empty slot).
+__device__ __forceinline__ int32_t lean_match(const lean_i4& qa, const lean_i4& qb, int32_t kk) {
+    int32_t t = -1;
+    unsigned long long m0, m1, m2, m3, m4, m5, m6, m7;
+    asm("v_cmp_eq_u32_e64 %8, %16, %17\n\t"
+        "v_cmp_eq_u32_e64 %7, %15, %17\n\t"
+        "v_cmp_eq_u32_e64 %6, %14, %17\n\t"
+        "v_cmp_eq_u32_e64 %5, %13, %17\n\t"
+        "v_cmp_eq_u32_e64 %4, %12, %17\n\t"
+        "v_cmp_eq_u32_e64 %3, %11, %17\n\t"
+        "v_cmp_eq_u32_e64 %2, %10, %17\n\t"
+        "v_cmp_eq_u32_e64 %1, %9, %17\n\t"
+        "v_cndmask_b32_e64 %0, %0, 7, %8\n\t"
+        "v_cndmask_b32_e64 %0, %0, 6, %7\n\t"
+        "v_cndmask_b32_e64 %0, %0, 5, %6\n\t"
+        "v_cndmask_b32_e64 %0, %0, 4, %5\n\t"
+        "v_cndmask_b32_e64 %0, %0, 3, %4\n\t"
+        "v_cndmask_b32_e64 %0, %0, 2, %3\n\t"
+        "v_cndmask_b32_e64 %0, %0, 1, %2\n\t"
+        "v_cndmask_b32_e64 %0, %0, 0, %1"
+        : "+v"(t), "=&s"(m0), "=&s"(m1), "=&s"(m2), "=&s"(m3), "=&s"(m4), "=&s"(m5), "=&s"(m6), "=&s"(m7)
+        : "v"(qa.x), "v"(qa.y), "v"(qa.z), "v"(qa.w), "v"(qb.x), "v"(qb.y), "v"(qb.z), "v"(qb.w), "v"(kk));
+    return t;
+}
+
+// The home bucket's first slot: jm::mix64 of the sign-extended key, of which a segment of at most 2^24 slots needs the
+// low 24 bits only. Bit for bit mix64's, with half of its 32-bit multiplies: the key's upper word is 0 or ~0, so its
+// products are a select; the last product is needed to bit 55, which 24-bit multiplies give for its two upper terms.
+__device__ __forceinline__ uint32_t lean_home(int32_t k, uint32_t smask) {
+    constexpr uint32_t c1l = 0x1ce4e5b9u, c1h = 0xbf58476du, c2l = 0x133111ebu, c2h = 0x94d049bbu;
+    const uint32_t s = (uint32_t)(k >> 31);
+    const uint32_t xlo = (uint32_t)k ^ (((uint32_t)k >> 30) | (s << 2));   // x = z ^ (z >> 30); its upper word is s & ~3
+    const unsigned long long p = (unsigned long long)xlo * c1l;
+    const uint32_t z1lo = (uint32_t)p;
+    const uint32_t z1hi = (uint32_t)(p >> 32) + xlo * c1h + (s & (0u - 4u * c1l));
+    const uint32_t ylo = z1lo ^ ((z1lo >> 27) | (z1hi << 5));              // y = z1 ^ (z1 >> 27)
+    const uint32_t yhi = z1hi ^ (z1hi >> 27);
+    const unsigned long long q = (unsigned long long)ylo * c2l;
+    const uint32_t z2lo = (uint32_t)q;
+    const uint32_t z2hi = (uint32_t)(q >> 32) + __umul24(ylo, c2h) + __umul24(yhi, c2l);   // low 24 bits
+    const uint32_t h = z2lo ^ ((z2lo >> 31) | (z2hi << 1));                // z2 ^ (z2 >> 31), low 25 bits
+    return h & smask & ~(uint32_t)(kBucket - 1);
+}
+
+// Minimum (unsigned) or maximum (signed) over the wave's 64 lanes, as a scalar: four DPP steps reduce each row of 16
+// lanes (pairs, quads, half rows, rows), the four rows meet in scalar registers. All lanes must be active.
+template <bool kMax>
+__device__ __forceinline__ int lean_wave_red(int v) {
+    auto step = [](int x, int y) { return kMax ? max(x, y) : (int)min((uint32_t)x, (uint32_t)y); };
+    v = step(v, __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xf, 0xf, true));    // quad_perm:[1,0,3,2]
+    v = step(v, __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xf, 0xf, true));    // quad_perm:[2,3,0,1]
+    v = step(v, __builtin_amdgcn_update_dpp(0, v, 0x141, 0xf, 0xf, true));   // row_half_mirror
+    v = step(v, __builtin_amdgcn_update_dpp(0, v, 0x140, 0xf, 0xf, true));   // row_mirror
+    return step(step(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)),
+                step(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
+}
+
+template <int IT, int BT, int SL, int TH>
+__device__ __forceinline__ void combine3_lean(const CombineArgs& a, const EngineConst& c) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    static_assert(IT % BT == 0, "whole batches");
+    static_assert(TH / kSub == 64, "one wave per sub-bucket");
+    constexpr int kWaves = TH / 64;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int p = blockIdx.x;
+    const int seg = 1 << a.seg_log;
+    const uint32_t smask = (uint32_t)seg - 1u;
+    __shared__ StragL s_strag[kStragL];
+    __shared__ int s_sn;
+    // LDS, at the general body's offsets (push_v2 sizes one block for both): key image [seg] i32 (swizzled, kswz32),
+    // COUNT [SL][seg] u32, SUM [SL][seg] u64, s_mm: the block's slice range of a chunk {min, max} x 3 (below), s_new
+    int32_t* lkey = (int32_t*)smem;
+    uint32_t* lcnt = (uint32_t*)(smem + (size_t)seg * 8);
+    unsigned long long* lacc = (unsigned long long*)(smem + (size_t)seg * 8 + (size_t)SL * seg * 4);
+    int* s_mm = (int*)(smem + (size_t)seg * 8 + (size_t)SL * seg * 4 + (size_t)SL * seg * 8);
+    int* s_new = s_mm + 4 * kWaves;
+    long long pt = clock64();
+    long long pacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#define PMARK(k) do { if (KPROF(a.prof)) { const long long _t = clock64(); pacc[k] += _t - pt; pt = _t; } } while (0)
+    unsigned long long* gkeys = a.key_table + ((int64_t)p << a.seg_log);
+    for (int i = tid; i < seg; i += TH) lkey[kswz32((uint32_t)i)] = lean_key_image(gkeys[i]);
+    for (int i = tid; i < SL * seg; i += TH) { lcnt[i] = 0; lacc[i] = 0ull; }
+    if (tid == 0) { *s_new = 0; s_sn = 0; }
+    if (tid < 3) { s_mm[2 * tid] = 0x7fffffff; s_mm[2 * tid + 1] = -1; }
+    constexpr int64_t kChunk = (int64_t)IT * 64;
+    // (the wave's own count, as a scalar: whole chunks are loaded without a bounds test per entry)
+    const int my_cnt = __builtin_amdgcn_readfirstlane((int)min((int64_t)a.b_cnt[p * kSub + wv], a.capb));
+    const int64_t boff = (int64_t)bucket_base(p, wv, a.np, a.sub_major) * a.capb;
+    int64_t cnt = 0;
+    for (int s2 = 0; s2 < kSub; ++s2) cnt = max(cnt, min((int64_t)a.b_cnt[p * kSub + s2], a.capb));
+    const gc_u64_ptr bk = (const gc_u64_ptr)(a.b_key + boff);
+    const __attribute__((address_space(1))) uint16_t* br = (const __attribute__((address_space(1))) uint16_t*)(a.b_rel + boff);
+    int lo = 0x7fffffff;
+    auto flush = [&](int rel) {   // merge window slice `rel` into HBM (the general body's flush for COUNT + one ADD_I64)
+        constexpr int kPer = 4096 / TH;   // seg <= 4096
+        const int w = rel & (SL - 1);
+        const int32_t slot = (rel >= 0 && rel < kRelCap) ? a.rel2slot[rel] : -1;
+        g_u64* base = slot >= 0 ? (g_u64*)a.slot_base[slot] : nullptr;
+        const bool fresh = slot >= 0 && a.relfresh && a.relfresh[rel];
+        uint32_t k[kPer];
+        unsigned long long x[kPer];
+        int64_t g[kPer];
+#pragma unroll
+        for (int m = 0; m < kPer; ++m) {
+            const int i = tid + m * TH;
+            k[m] = 0; x[m] = 0ull;
+            g[m] = ((int64_t)p << a.seg_log) + i;
+            if (i < seg) { k[m] = lcnt[w * seg + i]; lcnt[w * seg + i] = 0; }
+            if (k[m]) { x[m] = lacc[(size_t)w * seg + i]; lacc[(size_t)w * seg + i] = 0ull; }
+        }
+        if (!base) return;
+        g_u64* col = base + a.stride;
+        unsigned long long old[kPer], old1[kPer];
+#pragma unroll
+        for (int m = 0; m < kPer; ++m) {
+            old[m] = (k[m] && !fresh) ? base[g[m]] : 0ull;
+            old1[m] = (k[m] && !fresh) ? col[g[m]] : 0ull;
+        }
+#pragma unroll
+        for (int m = 0; m < kPer; ++m) if (k[m]) { base[g[m]] = old[m] + k[m]; col[g[m]] = old1[m] + x[m]; }
+    };
+    __syncthreads();
+    // register double buffer: n* = chunk in flight, the packed entries (key | value << 32) are unpacked at use
+    unsigned long long nkey[IT];
+    int nrel[IT];
+    auto load_chunk = [&](int64_t cb) {
+        if (cb + kChunk <= (int64_t)my_cnt) {   // a whole chunk: one address, the entries at constant offsets
+            const gc_u64_ptr pk = bk + cb + lane;
+            const __attribute__((address_space(1))) uint16_t* pr = br + cb + lane;
+#pragma unroll
+            for (int j = 0; j < IT; ++j) { nkey[j] = pk[j * 64]; nrel[j] = (int)pr[j * 64]; }
+        } else {
+#pragma unroll
+            for (int j = 0; j < IT; ++j) {
+                const int64_t i = cb + (int64_t)j * 64 + lane;
+                const bool ok = i < (int64_t)my_cnt;
+                nkey[j] = ok ? bk[i] : 0ull;
+                nrel[j] = ok ? (int)br[i] : -1;
+            }
+        }
+    };
+    load_chunk(0);
+    PMARK(0);
+    int it = 0;
+    for (int64_t cb = 0; cb < cnt; cb += kChunk, ++it) {
+        int32_t key[IT], val[IT];
+        int rel[IT];
+        const bool whole = cb + kChunk <= (int64_t)my_cnt;   // (wave-uniform) every entry of this wave's chunk is valid
+        uint32_t rminu = 0xffffffffu;       // (an invalid entry's -1 is the largest unsigned)
+        int rmax = -1;
+#pragma unroll
+        for (int j = 0; j < IT; ++j) {
+            key[j] = (int32_t)(uint32_t)nkey[j];
+            val[j] = (int32_t)(uint32_t)(nkey[j] >> 32);
+            rel[j] = nrel[j];
+            rminu = min(rminu, (uint32_t)rel[j]);
+            rmax = max(rmax, rel[j]);
+        }
+        PMARK(1);
+        if (cb + kChunk < cnt) load_chunk(cb + kChunk);
+        // the block's slice range of this chunk: every wave's range meets in one {min, max} pair of LDS (one lane's
+        // atomics), read back after the barrier. Three pairs in turn: the pair of chunk it + 1 is reset here, after the
+        // barrier of chunk it - 1 behind which its last readers (chunk it - 2) are done, before the barrier of chunk it
+        // ahead of which nobody writes it.
+        const int wmin = (int)min((uint32_t)lean_wave_red<false>((int)rminu), 0x7fffffffu), wmax = lean_wave_red<true>(rmax);
+        int* mm = s_mm + 2 * (it % 3);
+        if (lane == 0) { atomicMin(&mm[0], wmin); atomicMax(&mm[1], wmax); }
+        if (tid == 0) { int* nx = s_mm + 2 * ((it + 1) % 3); nx[0] = 0x7fffffff; nx[1] = -1; }
+        // hashes and home buckets before the barrier (pinned: the compiler otherwise sinks them behind it)
+        uint32_t hb[IT];
+#pragma unroll
+        for (int j = 0; j < IT; ++j) {
+            hb[j] = lean_home(key[j], smask);
+            consume(hb[j]);
+        }
+        PMARK(2);
+        __syncthreads();
+        PMARK(3);
+        const int cmin = __builtin_amdgcn_readfirstlane(mm[0]), cmax = __builtin_amdgcn_readfirstlane(mm[1]);
+        if (cmax < 0) continue;
+        if (lo == 0x7fffffff) lo = cmin;
+        if (cmax >= lo + SL) {              // slide the window up to the chunk's newest slice
+            while (cmax >= lo + SL) { flush(lo); ++lo; if (KPROF(a.prof)) pacc[7] += 1000; }
+            __syncthreads();
+        }
+        const int lo_c = lo;                // entries older than this are stragglers
+        PMARK(4);
+        if (KPROF(a.prof)) pacc[7] += 1;
+        // fast match: the home buckets of BT entries read together, then "found, and where" per entry. Physical quads
+        // (the swizzle exchanges a bucket's two quads): the logical slot is taken at the end.
+        // (hb[j] becomes the entry's slot once it is found: one register for both; a missed entry keeps its bucket)
+        uint32_t miss = 0;
+#pragma unroll
+        for (int j0 = IT - BT; j0 >= 0; j0 -= BT) {   // (descending: entry j's miss bit is shifted up to bit j)
+            lean_i4 qa[BT], qb[BT];
+#pragma unroll
+            for (int u = 0; u < BT; ++u) {
+                qa[u] = *(const lean_i4*)&lkey[hb[j0 + u]];
+                qb[u] = *(const lean_i4*)&lkey[hb[j0 + u] + 4];
+            }
+            lean_pin<BT>(qa, qb);
+#pragma unroll
+            for (int u = BT - 1; u >= 0; --u) {
+                const int32_t t = lean_match(qa[u], qb[u], key[j0 + u]);
+                const uint32_t b = hb[j0 + u];
+                // found: the logical slot; missed (t -1): some slot of the home bucket, the bucket is its & ~7
+                hb[j0 + u] = b + (((uint32_t)t ^ (b >> 4)) & 4u) + ((uint32_t)t & 3u);
+                miss = __builtin_amdgcn_alignbit(miss, (uint32_t)t, 31);   // miss << 1 | t's sign
+            }
+        }
+        // misses: each lane's lowest missed entry through the general probe, until no lane has one
+        uint32_t todo = miss;
+        if (!whole) {                       // (an invalid entry needs no slot; its bit stays in miss)
+            uint32_t ok = 0;
+#pragma unroll
+            for (int j = 0; j < IT; ++j) ok |= rel[j] >= 0 ? (1u << j) : 0u;
+            todo &= ok;
+        }
+        while (todo) {
+            const int jm_ = __builtin_ctz(todo);
+            todo &= todo - 1u;
+            int32_t kk = key[0];
+            uint32_t b = hb[0];
+#pragma unroll
+            for (int j = 1; j < IT; ++j) { kk = jm_ == j ? key[j] : kk; b = jm_ == j ? hb[j] : b; }
+            b &= ~(uint32_t)(kBucket - 1);
+            int32_t found = -1;
+            for (int round = 0; round <= (seg >> 2) && found < 0; ++round) {
+                const uint32_t f = ((b >> 6) & 1u) << 2;
+                const lean_i4 pa = *(const lean_i4*)&lkey[b + f];          // the quads in logical order
+                const lean_i4 pb = *(const lean_i4*)&lkey[b + (f ^ 4u)];
+                const int32_t eq = lean_match(pa, pb, kk), em = lean_match(pa, pb, kLeanEmpty);
+                if (eq >= 0) { found = (int32_t)(b + (uint32_t)eq); break; }
+                if (em >= 0) {                  // absent: insert at the first empty slot (CAS vs other lanes)
+                    const uint32_t sidx = b + (uint32_t)em;
+                    const int32_t old = atomicCAS(&lkey[kswz32(sidx)], kLeanEmpty, kk);
+                    if (old == kLeanEmpty) { found = (int32_t)sidx; atomicAdd(s_new, 1); break; }
+                    if (old == kk) { found = (int32_t)sidx; break; }
+                    continue;                   // lost the slot to another key: re-read this bucket
+                }
+                b = (b + kBucket) & smask;
+            }
+            if (found >= 0) miss &= ~(1u << jm_);
+#pragma unroll
+            for (int j = 0; j < IT; ++j) hb[j] = (jm_ == j && found >= 0) ? (uint32_t)found : hb[j];
+        }
+        // simple chunk (wave-uniform): every entry valid, found, in [lo_c, lo_c + SL)
+        uint32_t out = 0;                   // outside the window (invalid entries too: rel -1)
+#pragma unroll
+        for (int j = 0; j < IT; ++j) out |= (uint32_t)(rel[j] - lo_c) & ~(uint32_t)(SL - 1);
+        if (__builtin_amdgcn_ballot_w64((out | miss) != 0u) == 0ull) {
+#pragma unroll
+            for (int j = 0; j < IT; ++j) {
+                const uint32_t at = ((uint32_t)(rel[j] & (SL - 1)) << a.seg_log) + hb[j];
+                atomicAdd(&lcnt[at], 1u);
+                atomicAdd(&lacc[at], (unsigned long long)(int64_t)val[j]);
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < IT; ++j) {
+                if (rel[j] < 0 || rel[j] >= lo + SL) continue;
+                if (miss & (1u << j)) { a.st->key_full = 1; raise_error(a.st, FWA_E_OOM); continue; }
+                const int32_t local = (int32_t)hb[j];
+                const unsigned long long x0 = (unsigned long long)(int64_t)val[j];
+                if (rel[j] < lo_c) {
+                    // older than the window (its slice is already merged into HBM): listed in LDS and applied
+                    // with device atomics after the last merge
+                    if (KPROF(a.prof)) pacc[6] += 1000000;
+                    const uint32_t g = (uint32_t)(((int64_t)p << a.seg_log) + local);
+                    const int si = atomicAdd(&s_sn, 1);
+                    if (si < kStragL) s_strag[si] = StragL{g, 1u, rel[j], 0, x0, 0ull};
+                    else strag_apply(a, c, rel[j], g, 1u, x0, 0ull);
+                    continue;
+                }
+                const int w = rel[j] & (SL - 1);
+                atomicAdd(&lcnt[w * seg + local], 1u);
+                atomicAdd(&lacc[(size_t)w * seg + local], x0);
+            }
+        }
+        PMARK(5);
+    }
+    __syncthreads();
+    if (lo != 0x7fffffff)
+        for (int r = lo; r < lo + SL; ++r) flush(r);
+    __syncthreads();                    // every merge of this block stored before the stragglers' atomics
+    if (tid == 0 && s_sn) atomicAdd(&a.st->strag_n, s_sn);
+    for (int t = tid; t < min(s_sn, kStragL); t += TH) {
+        const StragL se = s_strag[t];
+        strag_apply(a, c, se.rel, se.g, se.n, se.x0, se.x1);
+    }
+    if (*s_new) {                       // publish the slots this block filled (exclusive owner of this segment)
+        for (int i = tid; i < seg; i += TH) {
+            const int32_t k32 = lkey[kswz32((uint32_t)i)];
+            if (k32 != kLeanEmpty && gkeys[i] == kEmptyKey) gkeys[i] = (unsigned long long)(int64_t)k32;
+        }
+        if (tid == 0) atomicAdd(&a.st->n_keys, (unsigned long long)*s_new);
+    }
+    if (KPROF(a.prof) && tid == 0) for (int q = 0; q < 8; ++q) a.prof[(int64_t)p * 8 + q] = pacc[q];
+#undef PMARK
+}
+
 // LAYOUT: the accumulator columns, fixed at compile time for the common shapes so the per-record
 // path has no descriptor switch (a runtime switch over 8 columns cost ~1000 scalar instructions per
 // record from SGPR spills): 1 = COUNT + one ADD_I64 fed by value slot 0 (SUM/AVG over BIGINT);
 // 2 = COUNT only; 0 = generic (descriptor table in LDS, one column per loop trip).
 // MP: window passes (below) for chunks spanning more slices than the window; chosen per handle once a push
 // saw many stragglers (small HOP/CUMULATE slices), since the passes cost registers the common case needs.
-template <int IT, int SL, int NV, int TH, int LAYOUT, int PRE = 0, int MP = 0, int NW = 0>
+// LEAN: the lean body above (narrow COUNT + BIGINT SUM entries only) with first probes in batches of LEAN entries;
+// 0: the general body.
+template <int IT, int SL, int NV, int TH, int LAYOUT, int PRE = 0, int MP = 0, int NW = 0, int LEAN = 0>
 __global__ void __launch_bounds__(TH, 1) combine3_kernel(CombineArgs a, const EngineConst* __restrict__ cp) {
+    if constexpr (LEAN != 0) {
+        static_assert(NW == 1 && LAYOUT == 1 && NV == 1 && PRE == 0 && MP == 0, "lean body: narrow COUNT + SUM entries");
+        combine3_lean<IT, LEAN, SL, TH>(a, *cp);
+        return;
+    }
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int kWaves = TH / 64;
     constexpr int LPS = TH / kSub;     // lanes per sub-bucket (64: one wave per sub; 32: two subs per wave)

@@ -152,7 +152,8 @@ def _check(rc, h=None, what=""):
 OPTIONS = {"skew_merge": 1, "window_passes": 2, "narrow_entries": 3, "session_cells": 4, "out_min_rows": 5,
            "partials_one_pass": 6, "sp_table": 7, "sp_fmax": 8, "sp_budget": 9, "profile": 10,
            "session_path": 11, "ingest_variant": 12, "slide_carried": 13, "fire_partials": 14, "dec_wrap_null": 15,
-           "fused_fires": 16, "reset_launches": 17, "distinct_slots": 18, "distinct_live": 19, "distinct_rebuilds": 20}
+           "fused_fires": 16, "reset_launches": 17, "distinct_slots": 18, "distinct_live": 19, "distinct_rebuilds": 20,
+           "stragglers": 21, "key_table_digest": 22}
 # options applied to every new handle of this process before its own (test tooling sets these, e.g.
 # tests/forced_modes_check.py); empty in production
 DEFAULT_OPTIONS = {}

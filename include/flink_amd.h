@@ -557,7 +557,9 @@ enum fwa_option {
     FWA_OPT_SESSION_PATH = 11,   /* read only: the path of the last session push -- 0 general, 1 sort-based cells,
                                     2 cell pre-aggregation (fwa_get_option) */
     FWA_OPT_INGEST_VARIANT = 12, /* diagnostic A/B switches of the ingest kernels (0 default); bit 0: the combiner
-                                    reads a slot it merges into even when no record reached it yet; bit 8 (256): the
+                                    reads a slot it merges into even when no record reached it yet; bit 1 (2): narrow COUNT + BIGINT
+                                    SUM entries go through the combiner's general body instead of its lean one (4-byte
+                                    keys in LDS, batched first probes, misses deferred); bit 8 (256): the
                                     tumbling fire as one kernel block per (window, key chunk) with an uploaded window
                                     table, a memset of its row counter and reset_slots_kernel for the retired slots,
                                     instead of the one-pass fire that retires its slots itself, and every push uploads
@@ -576,8 +578,12 @@ enum fwa_option {
                                     first push; default: sized from the first push); tests force growth with it.
                                     fwa_get_option: the current size */
     FWA_OPT_DISTINCT_LIVE = 19,  /* read only: set entries of unfired windows counted at the last rebuild */
-    FWA_OPT_DISTINCT_REBUILDS = 20 /* read only: rebuilds of the set (growth, dropping fired windows' entries, and one
+    FWA_OPT_DISTINCT_REBUILDS = 20, /* read only: rebuilds of the set (growth, dropping fired windows' entries, and one
                                       per fwa_snapshot, which reads the live entries out of a rebuild) */
+    FWA_OPT_STRAGGLERS = 21,     /* read only: bucket entries of the two-phase pushes so far that were older than their
+                                    combiner block's slice window and were applied after its last merge (fwa_get_option) */
+    FWA_OPT_KEY_TABLE_DIGEST = 22 /* read only: FNV-1a digest of the key table's words in slot order (fwa_get_option;
+                                     diagnostic: equal for two handles that placed every key in the same slot) */
 };
 int fwa_set_option(fwa_engine* e, int32_t option, int64_t value);
 /* The option's effective value: for the tri-state options 1 if the handle currently takes that path (forced, or
