@@ -87,6 +87,7 @@ CFG_LATE_INDICES = 0x2
 CFG_RECORD_LISTS = 0x4
 CFG_REDUCE = 0x8
 CFG_BY_LAST = 0x10
+CFG_DISTINCT_RANGE = 0x20
 
 PUSH_DEVICE_PTRS = 0x1
 PUSH_ASYNC = 0x2
@@ -163,12 +164,13 @@ def make_config(window_kind="TUMBLE", semantics="DATASTREAM", size_ms=10_000, sl
                 offset_ms=0, gap_ms=0, allowed_lateness_ms=0, aggs=(("COUNT", 0), ("SUM_I64", 0)),
                 key_kind=KEY_JAVA_LONG, max_parallelism=128, kg_start=0, kg_end=None, device=0,
                 output_on_device=0, key_capacity=0, max_batch=0, gap_col=None, tz=None, late_indices=False,
-                nullable_cols=(), record_lists=False, reduce=False, by_last=False):
+                nullable_cols=(), record_lists=False, reduce=False, by_last=False, distinct_range=False):
     """Build a Config struct. aggs: sequence of (agg name, value-column index). gap_col: value column of
     per-record session gaps (DynamicEventTimeSessionWindows). tz: [(utc_instant_ms, offset_ms), ...] shift
     time zone of a TIMESTAMP_LTZ rowtime (the struct keeps a pointer to a buffer held on the struct). reduce: a
     DataStream built-in reduction (FWA_CFG_REDUCE, WindowedStream.sum/min/max/minBy/maxBy); by_last: minBy / maxBy
-    ties go to the last element (FWA_CFG_BY_LAST)."""
+    ties go to the last element (FWA_CFG_BY_LAST). distinct_range: allow COUNT_DISTINCT on a Table HOP / CUMULATE
+    handle, counted from the set at every fire (FWA_CFG_DISTINCT_RANGE)."""
     c = Config()
     c.abi_version = FWA_ABI_VERSION
     c.window_kind = WINDOW_KINDS[window_kind] if isinstance(window_kind, str) else int(window_kind)
@@ -200,6 +202,8 @@ def make_config(window_kind="TUMBLE", semantics="DATASTREAM", size_ms=10_000, sl
         c.flags |= CFG_REDUCE
     if by_last:
         c.flags |= CFG_BY_LAST
+    if distinct_range:
+        c.flags |= CFG_DISTINCT_RANGE
     for col in nullable_cols:                             # value columns that may hold SQL NULLs
         c.nullable_cols |= 1 << col
     if gap_col is not None:

@@ -10,7 +10,8 @@
 // first runs distinct_mark_kernel over the batch: it inserts (key, value, slice, column) into one device-resident
 // open-addressing set per handle and writes mark[i] = 1 iff this insert created the entry. Phase P / A, the fire
 // kernels, record lists and snapshots then see an ordinary 64-bit sum. A window of several slices (HOP, CUMULATE,
-// SESSION) would need the union of per-slice sets at the fire, which is not a sum: those are refused.
+// SESSION) needs the union of per-slice sets at the fire, which is not a sum: HOP and CUMULATE take it there under
+// FWA_CFG_DISTINCT_RANGE (range mode, below), everything else is refused.
 //
 // The set. One 32-byte aligned entry per slot, three 64-bit words used (the fourth pads the entry to one 32-byte
 // sector, so a probe is one aligned vector load):
@@ -37,6 +38,30 @@
 // allocation of the table's size in the steady state). The bound becomes the exact count. Firing a window costs
 // nothing: its entries are garbage the next rebuild drops, so the set holds live entries + one batch (x <= 4 for the
 // load factor and the rounding).
+//
+// Range mode (FWA_CFG_DISTINCT_RANGE on a Table HOP or CUMULATE handle). A hop window is a range of slices and the
+// carried window sums add and subtract whole slices, so a per-slice additive mark cannot count it: a value present in
+// slices 1 and 3 is the "first" of each slice but must count once in [1, 3], once in [2, 5] and once in [0, 1] -- no
+// fixed 0/1 per (value, slice) gives all three, the union has to be taken per window. So the count moves from the push
+// to the fire, and the set changes the meaning of its slice field only:
+//   word 2  tag's slice field = the block number B = q >> 6 (arithmetic), q the slice number of the ingest directory
+//   word 3  occupancy bitmap: bit q & 63 is set iff the value occurred for the key in slice q
+// One entry per (key, value, column, block of 64 slices). B needs six bits fewer than q, so the 64 ms limit does not
+// apply. The push runs distinct_mark_range_kernel (upsert, then atomicOr of the bit only when a plain load does not
+// show it: duplicates stay atomic-free) and writes no marked column; dist_plan rewrites COUNT_DISTINCT(c) into COUNT(*)
+// (a BIGINT that is never NULL and needs no value column), so the handle keeps its ingest and its fire, and every
+// firing step of fwa_advance_watermark then calls dist_range_count before it retires slices:
+//   dist_rows_index_kernel   zeroes the distinct columns of the step's rows and indexes the rows by (key, window end) in
+//                            a u32 open-addressing table (plan-owned scratch)
+//   dist_range_count_kernel  scans the set; an entry whose bits meet a fired window's slice range counts 1 for that
+//                            window iff no earlier block of the window holds the same (key, value, column) with bits in
+//                            the range (a read-only probe per earlier block: at most ceil(N / 64) for N slices), so
+//                            each value is counted by exactly one of its entries; the count goes to the row by atomicAdd
+// A live entry without a row is a broken invariant (accepted record => COUNT(*) > 0 => a row): the step fails.
+// Rebuilds carry word 3 (the live cut is the block of q_min: a block is live while its highest slice is); the snapshot
+// section keeps its layout, one entry per set bit, and restore folds them back.
+
+struct DistWin { int64_t q_lo, q_hi, end; };   // a fired window: its slice range and its end as the fire emits it
 
 struct DistinctPlan {
     fwa_config ucfg;                       // the caller's configuration (fwa_get_config)
@@ -53,14 +78,24 @@ struct DistinctPlan {
     char* d_stage = nullptr;               // host pushes: every input column, staged once
     size_t stage_bytes = 0;
     unsigned long long* d_ctr = nullptr;   // [0] entries counted / created, [1] inserts that found no slot,
-    unsigned long long* h_ctr = nullptr;   // [2] entries the last marking pass created (h_ctr[2]: its pinned landing)
+    unsigned long long* h_ctr = nullptr;   // [2] entries the last marking pass created (h_ctr[2]: its pinned landing),
+                                           // [3] range mode: counted entries whose (key, window) has no row
     unsigned int* d_bcnt = nullptr;        // table scans: live entries per block [kDistScanGrid], then (8-byte aligned)
     unsigned long long* d_bpre = nullptr;  // ... their exclusive prefix [kDistScanGrid]
-    unsigned long long* d_side = nullptr;  // in-place rebuild: the live entries, [3][side_cap]
+    unsigned long long* d_side = nullptr;  // in-place rebuild: the live entries, [3][side_cap] (range mode: [4][side_cap])
     int64_t side_cap = 0;
     hipEvent_t ev[3] = {};                 // marking pass begin / end (timed), its created-count copy
     bool timing = false;                   // ev[0..1] hold a marking pass not yet added to ingest_ms
     int64_t last_add = 0;                  // the last marking pass's share of `bound`, until its exact count replaces it
+    // range mode (FWA_CFG_DISTINCT_RANGE, HOP / CUMULATE): word 3 is a slice bitmap, counts are taken at the fire
+    bool range = false;
+    unsigned int* d_rtab = nullptr;        // the step's rows by (key, window end): row + 1 per slot, [rtab_cap]
+    int64_t rtab_cap = 0;
+    DistWin* d_wins = nullptr;             // the step's windows, [wins_cap]
+    int64_t wins_cap = 0;
+    hipEvent_t rev[3] = {};                // row-index pass begin, range-count pass begin / end
+    double index_ms = 0.0, count_ms = 0.0; // their device time so far (also part of fire_ms)
+    int64_t count_steps = 0;               // firing steps counted
 };
 
 namespace {
@@ -79,8 +114,9 @@ __host__ __device__ __forceinline__ uint64_t dist_tag(int64_t q, uint64_t key, u
 }
 __host__ __device__ __forceinline__ int64_t dist_tag_q(uint64_t tag) { return (int64_t)tag >> 6; }
 
-// 1: this call created the entry, 0: it was there, -1: no slot (the host's bound makes that impossible)
-__device__ __forceinline__ int dist_insert(unsigned long long* tab, uint64_t smask, uint64_t k, uint64_t v, uint64_t t) {
+// 1: this call created the entry, 0: it was there, -1: no slot (the host's bound makes that impossible); *slot: where
+__device__ __forceinline__ int dist_upsert(unsigned long long* tab, uint64_t smask, uint64_t k, uint64_t v, uint64_t t,
+                                           uint64_t* slot) {
     uint64_t i = dist_hash(k, v, t) & smask;
     for (uint64_t probe = 0; probe <= smask; ++probe, i = (i + 1) & smask) {
         unsigned long long* s = tab + 4 * i;
@@ -92,10 +128,42 @@ __device__ __forceinline__ int dist_insert(unsigned long long* tab, uint64_t sma
         if (c == 0ull) { c = atomicCAS(s + 1, 0ull, (unsigned long long)v); if (c == 0ull) c = v; }
         if (c != v) continue;
         c = s[2];
+        *slot = i;
         if (c == 0ull) { c = atomicCAS(s + 2, 0ull, (unsigned long long)t); if (c == 0ull) return 1; }
         if (c == t) return 0;
     }
     return -1;
+}
+__device__ __forceinline__ int dist_insert(unsigned long long* tab, uint64_t smask, uint64_t k, uint64_t v, uint64_t t) {
+    uint64_t slot;
+    return dist_upsert(tab, smask, k, v, t, &slot);
+}
+
+// Range mode: set `bits` in the bitmap of the slot dist_upsert returned; a plain load first, so a bit that is there
+// costs no atomic (a stale load can only miss a bit, which falls through to the atomicOr).
+__device__ __forceinline__ void dist_or_bits(unsigned long long* tab, uint64_t slot, unsigned long long bits) {
+    unsigned long long* w = tab + 4 * slot + 3;
+    if ((*w & bits) != bits) atomicOr(w, bits);
+}
+
+// Read-only probe: the slot of (k, v, t) or -1. It may stop at a slot whose key word is 0: words never change between
+// rebuilds, every insert of an earlier launch ran to its end, and no insert runs beside the caller.
+__device__ __forceinline__ int64_t dist_find(const unsigned long long* tab, uint64_t smask, uint64_t k, uint64_t v, uint64_t t) {
+    uint64_t i = dist_hash(k, v, t) & smask;
+    for (uint64_t probe = 0; probe <= smask; ++probe, i = (i + 1) & smask) {
+        const ulonglong2 kv = *reinterpret_cast<const ulonglong2*>(tab + 4 * i);
+        if (kv.x == 0ull) return -1;
+        if (kv.x == k && kv.y == v && tab[4 * i + 2] == t) return (int64_t)i;
+    }
+    return -1;
+}
+
+// The bits of block B that lie in the slice range [q_lo, q_hi] (the two must intersect).
+__device__ __forceinline__ unsigned long long dist_block_mask(int64_t q_lo, int64_t q_hi, int64_t B) {
+    const int64_t b0 = (int64_t)((uint64_t)B << 6);
+    const int lo = q_lo > b0 ? (int)(q_lo - b0) : 0;
+    const int hi = q_hi < b0 + 63 ? (int)(q_hi - b0) : 63;
+    return (~0ull >> (63 - hi)) & (~0ull << lo);
 }
 
 struct DistMarkArgs {
@@ -129,6 +197,35 @@ __global__ void __launch_bounds__(256) distinct_mark_kernel(DistMarkArgs a, cons
                 created += r > 0 ? 1u : 0u;
             }
             a.mark[d][i] = m;
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) created += __shfl_down(created, o);    // the whole wave is back here
+    if ((threadIdx.x & 63) == 0 && created) atomicAdd(a.ctr + 2, (unsigned long long)created);
+}
+
+// Range mode, one thread per record: upsert (key, value, block of q, column) and set bit q & 63 of its bitmap. No marked
+// column is written (a.mark is unused).
+// The q >= q_min filter is garbage control only. A record it skips is one the ingest drops: every window containing its
+// slice has fired, so its bit lies in no window that fires again and is never read. The opposite error -- skipping a
+// record the ingest accepts -- would lose a value, and cannot happen: q_min comes from accept_threshold at the handle's
+// watermark (dist_qmin), the function and the watermark the ingest directory's thresholds come from, and "unknown"
+// (LONG_MIN) filters nothing.
+__global__ void __launch_bounds__(256) distinct_mark_range_kernel(DistMarkArgs a, const EngineConst* __restrict__ cp) {
+    const EngineConst& c = *cp;
+    unsigned int created = 0;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t q = sp_slice(c, assign_ts(c, a.ts[i]));
+        if (q < a.q_min) continue;
+        const uint64_t key = (uint64_t)a.keys[i];
+        const unsigned long long bit = 1ull << (q & 63);
+        for (int d = 0; d < a.nd; ++d) {
+            if (a.nul[d] && a.nul[d][i]) continue;
+            const uint64_t v = (uint64_t)a.src[d][i];
+            uint64_t slot = 0;
+            const int r = dist_upsert(a.tab, a.smask, key ? key : 1ull, v ? v : 1ull, dist_tag(q >> 6, key, v, d), &slot);
+            if (r < 0) { atomicAdd(a.ctr + 1, 1ull); continue; }
+            dist_or_bits(a.tab, slot, bit);
+            created += r > 0 ? 1u : 0u;
         }
     }
     for (int o = 32; o > 0; o >>= 1) created += __shfl_down(created, o);    // the whole wave is back here
@@ -183,7 +280,9 @@ __global__ void __launch_bounds__(64) distinct_prefix_kernel(const unsigned int*
 }
 
 // Rebuild into a new table: the entries of unfired windows re-inserted; ctr[0] receives the entries created there (the
-// exact live count), one atomic per wave.
+// exact live count), one atomic per wave. q_min is the live cut in the tag's unit (range mode, R: blocks, and the
+// bitmap moves with its entry).
+template <bool R>
 __global__ void __launch_bounds__(256) distinct_rebuild_kernel(const unsigned long long* tab, int64_t slots, int64_t q_min,
                                                               unsigned long long* ntab, uint64_t nsmask,
                                                               unsigned long long* ctr) {
@@ -192,8 +291,10 @@ __global__ void __launch_bounds__(256) distinct_rebuild_kernel(const unsigned lo
         const ulonglong2 kv = *reinterpret_cast<const ulonglong2*>(tab + 4 * i);
         const unsigned long long t = tab[4 * i + 2];
         if (t != 0ull && dist_tag_q(t) >= q_min) {
-            const int r = dist_insert(ntab, nsmask, kv.x, kv.y, t);
+            uint64_t slot = 0;
+            const int r = dist_upsert(ntab, nsmask, kv.x, kv.y, t, &slot);
             if (r < 0) atomicAdd(ctr + 1, 1ull);
+            else if (R) dist_or_bits(ntab, slot, tab[4 * i + 3]);
             made += r > 0 ? 1u : 0u;
         }
     }
@@ -203,7 +304,8 @@ __global__ void __launch_bounds__(256) distinct_rebuild_kernel(const unsigned lo
 
 // In-place rebuild, first half: block b's entries of unfired windows move to side[3][cap] from bpre[b] on (an LDS
 // cursor orders them inside the block) and every slot is cleared in the same pass (each thread owns its slot: nothing
-// inserts meanwhile). ctr[0] receives the entries moved.
+// inserts meanwhile). ctr[0] receives the entries moved. Range mode (R): side[4][cap], the bitmap as the fourth word.
+template <bool R>
 __global__ void __launch_bounds__(256) distinct_extract_kernel(unsigned long long* tab, int64_t slots, int64_t q_min,
                                                               unsigned long long* side, int64_t cap,
                                                               const unsigned long long* bpre, unsigned long long* ctr) {
@@ -217,13 +319,15 @@ __global__ void __launch_bounds__(256) distinct_extract_kernel(unsigned long lon
     for (int64_t i0 = lo; i0 < hi; i0 += 256) {           // (uniform per block: every lane takes every iteration)
         const int64_t i = i0 + threadIdx.x;
         ulonglong2 kv = make_ulonglong2(0ull, 0ull);
-        unsigned long long t = 0ull;
+        unsigned long long t = 0ull, bits = 0ull;
         if (i < hi) {
             kv = *reinterpret_cast<const ulonglong2*>(tab + 4 * i);
             t = tab[4 * i + 2];
+            if (R) bits = tab[4 * i + 3];
             if (kv.x | kv.y | t) {
                 *reinterpret_cast<ulonglong2*>(tab + 4 * i) = make_ulonglong2(0ull, 0ull);
                 tab[4 * i + 2] = 0ull;
+                if (R) tab[4 * i + 3] = 0ull;
             }
         }
         const bool livee = t != 0ull && dist_tag_q(t) >= q_min;
@@ -234,7 +338,10 @@ __global__ void __launch_bounds__(256) distinct_extract_kernel(unsigned long lon
         off = __shfl(off, 0);
         if (livee) {
             const int64_t pos = base + off + __popcll(b & ((1ull << lane) - 1ull));
-            if (pos < cap) { side[pos] = kv.x; side[cap + pos] = kv.y; side[2 * cap + pos] = t; }
+            if (pos < cap) {
+                side[pos] = kv.x; side[cap + pos] = kv.y; side[2 * cap + pos] = t;
+                if (R) side[3 * cap + pos] = bits;
+            }
             else atomicAdd(ctr + 1, 1ull);
         }
     }
@@ -243,18 +350,112 @@ __global__ void __launch_bounds__(256) distinct_extract_kernel(unsigned long lon
 }
 
 // Restore and the in-place rebuild's second half: entries given as their three stored words (w[3][n]), inserted
-// without marking.
+// without marking. Range mode (R): w[4][n], the fourth word ORed into the entry's bitmap (restore folds one bit each).
+template <bool R>
 __global__ void __launch_bounds__(256) distinct_insert_side_kernel(const unsigned long long* w, int64_t stride, int64_t n,
                                                                   unsigned long long* tab, uint64_t smask,
                                                                   unsigned long long* ctr) {
     unsigned int made = 0;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const int r = dist_insert(tab, smask, w[i], w[stride + i], w[2 * stride + i]);
+        uint64_t slot = 0;
+        const int r = dist_upsert(tab, smask, w[i], w[stride + i], w[2 * stride + i], &slot);
         if (r < 0) atomicAdd(ctr + 1, 1ull);
+        else if (R) dist_or_bits(tab, slot, w[3 * stride + i]);
         made += r > 0 ? 1u : 0u;
     }
     for (int o = 32; o > 0; o >>= 1) made += __shfl_down(made, o);
     if ((threadIdx.x & 63) == 0 && made) atomicAdd(ctr, (unsigned long long)made);
+}
+
+// ---- range mode: the count of a firing step ----
+
+struct DistRangeArgs {
+    const unsigned long long* tab;
+    int64_t slots;
+    uint64_t smask;
+    const DistWin* wins;
+    int32_t nw;
+    int32_t na;                            // distinct aggregates
+    const int64_t* o_key;
+    const int64_t* o_end;
+    int64_t row0, nrows;                   // the step's rows: [row0, row0 + nrows)
+    unsigned int* rtab;
+    uint32_t rmask;                        // row-table slots - 1
+    unsigned long long* o_agg[FWA_MAX_AGGS];   // output column of distinct aggregate a
+    int32_t agg_d[FWA_MAX_AGGS];               // ... and the ordinal of its source column
+    unsigned long long* ctr;
+};
+
+__device__ __forceinline__ uint32_t dist_row_hash(int64_t key, int64_t end) {
+    return (uint32_t)jm::mix64((uint64_t)key ^ jm::mix64((uint64_t)end));
+}
+
+// One thread per emitted row: its distinct columns start from 0 (the fire wrote COUNT(*) there) and the row enters the
+// row table under (key, window end), which is unique within a step.
+__global__ void __launch_bounds__(256) dist_rows_index_kernel(DistRangeArgs a) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.nrows) return;
+    const int64_t row = a.row0 + i;
+    for (int j = 0; j < a.na; ++j) a.o_agg[j][row] = 0ull;
+    uint32_t h = dist_row_hash(a.o_key[row], a.o_end[row]) & a.rmask;
+    for (uint32_t probe = 0; probe <= a.rmask; ++probe, h = (h + 1) & a.rmask)
+        if (atomicCAS(a.rtab + h, 0u, (unsigned int)(i + 1)) == 0u) return;
+}
+
+// Row of (key, end) relative to row0, or -1. Equality reads the row's own columns.
+__device__ __forceinline__ int64_t dist_row_find(const DistRangeArgs& a, int64_t key, int64_t end) {
+    uint32_t h = dist_row_hash(key, end) & a.rmask;
+    for (uint32_t probe = 0; probe <= a.rmask; ++probe, h = (h + 1) & a.rmask) {
+        const unsigned int r = a.rtab[h];
+        if (r == 0u) return -1;
+        const int64_t row = a.row0 + (int64_t)r - 1;
+        if (a.o_key[row] == key && a.o_end[row] == end) return row;
+    }
+    return -1;
+}
+
+// One thread per slot of the set (block ranges as dist_block_range; the entry read as two aligned 16-byte loads). A
+// live entry (key, value, B, d, bits) is tried against the step's windows, staged in LDS kDistWinLds at a time (the
+// common step fires one window): with m = bits & the window's range inside block B non-zero, it is the window's first
+// block of its (key, value, d) iff no earlier block B' in [q_lo >> 6, B) holds an entry with bits in the range -- one
+// read-only probe per earlier block, none for a window inside one block. Only the first block counts: +1 on the row of
+// (key, window end) for every aggregate over column d. Entries without a row are counted in ctr[3] (one atomic per wave).
+constexpr int kDistWinLds = 128;
+__global__ void __launch_bounds__(256) dist_range_count_kernel(DistRangeArgs a) {
+    __shared__ DistWin s_win[kDistWinLds];
+    int64_t lo, hi;
+    dist_block_range(a.slots, &lo, &hi);
+    unsigned int miss = 0;
+    for (int w0 = 0; w0 < a.nw; w0 += kDistWinLds) {       // (uniform per block)
+        const int cn = a.nw - w0 < kDistWinLds ? a.nw - w0 : kDistWinLds;
+        __syncthreads();
+        for (int w = threadIdx.x; w < cn; w += 256) s_win[w] = a.wins[w0 + w];
+        __syncthreads();
+        for (int64_t i = lo + threadIdx.x; i < hi; i += 256) {
+            const ulonglong2 tb = *reinterpret_cast<const ulonglong2*>(a.tab + 4 * i + 2);
+            if (tb.x == 0ull || tb.y == 0ull) continue;
+            const ulonglong2 kv = *reinterpret_cast<const ulonglong2*>(a.tab + 4 * i);
+            const int64_t B = dist_tag_q(tb.x);
+            const int64_t b0 = (int64_t)((uint64_t)B << 6);
+            for (int w = 0; w < cn; ++w) {
+                const int64_t q_lo = s_win[w].q_lo, q_hi = s_win[w].q_hi;
+                if (q_hi < b0 || q_lo > b0 + 63) continue;
+                if (!(tb.y & dist_block_mask(q_lo, q_hi, B))) continue;
+                bool first = true;
+                for (int64_t Bp = q_lo >> 6; first && Bp < B; ++Bp) {
+                    const int64_t s = dist_find(a.tab, a.smask, kv.x, kv.y, (tb.x & 63ull) | ((uint64_t)Bp << 6));
+                    if (s >= 0 && (a.tab[4 * s + 3] & dist_block_mask(q_lo, q_hi, Bp))) first = false;
+                }
+                if (!first) continue;
+                const int64_t row = dist_row_find(a, (tb.x & 8ull) ? 0 : (int64_t)kv.x, s_win[w].end);
+                if (row < 0) { ++miss; continue; }
+                const int d = (int)(tb.x & 7ull);
+                for (int j = 0; j < a.na; ++j) if (a.agg_d[j] == d) atomicAdd(a.o_agg[j] + row, 1ull);
+            }
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) miss += __shfl_down(miss, o);          // the whole wave is back here
+    if ((threadIdx.x & 63) == 0 && miss) atomicAdd(a.ctr + 3, (unsigned long long)miss);
 }
 
 // ---- host ----
@@ -276,12 +477,38 @@ int dist_plan(const fwa_config* u, DistinctPlan* P, fwa_config* icfg, std::strin
         if (s.kind != FWA_COUNT && (s.col < 0 || s.col >= FWA_MAX_COLS)) return FWA_E_ARG;
     }
     auto no = [&](const char* m) { *why = std::string("COUNT(DISTINCT): ") + m; return FWA_E_UNSUPPORTED; };
-    if (u->window_kind != FWA_TUMBLE)
-        return no("only TUMBLE windows (a window of several slices needs the union of their sets, which is not additive)");
+    const bool hop = u->window_kind == FWA_SLIDE || u->window_kind == FWA_CUMULATE;
+    if (hop && !(u->flags & FWA_CFG_DISTINCT_RANGE))
+        return no("SLIDE / CUMULATE windows need FWA_CFG_DISTINCT_RANGE (a window of several slices needs the union of "
+                  "their sets, which is not additive: the flag takes the count from the set at every fire)");
+    if (u->window_kind != FWA_TUMBLE && !hop)
+        return no("only TUMBLE windows, and SLIDE / CUMULATE under FWA_CFG_DISTINCT_RANGE (a window of several slices "
+                  "needs the union of their sets, which is not additive)");
     if (u->semantics != FWA_SEM_TABLE) return no("a Table aggregate (FWA_SEM_TABLE)");
     if (u->flags & FWA_CFG_REDUCE) return no("not a DataStream reduction");
     if (u->key_kind == FWA_KEY_PREHASHED)
         return no("PREHASHED keys are not supported (the set keeps no hash per entry to place it in a key group)");
+    if (hop) {
+        // range mode: COUNT_DISTINCT(c) -> COUNT(*), a BIGINT that is never NULL, shares column 0 and reads no value
+        // column, so nothing is remapped and the handle keeps the two-phase ingest and the carried HOP sums; the fire
+        // overwrites the column from the set (dist_range_count)
+        P->range = true;
+        bool read[FWA_MAX_COLS] = {};
+        for (int j = 0; j < u->num_aggs; ++j)
+            if (u->aggs[j].kind != FWA_COUNT && u->aggs[j].kind != FWA_COUNT_DISTINCT) read[u->aggs[j].col] = true;
+        for (int j = 0; j < u->num_aggs; ++j) {
+            const fwa_agg_spec& s = u->aggs[j];
+            if (s.kind != FWA_COUNT_DISTINCT) continue;
+            P->mask |= (int64_t)1 << j;
+            int d = -1;
+            for (int i = 0; i < P->nd; ++i) if (P->src[i] == s.col) d = i;
+            if (d < 0) { d = P->nd++; P->src[d] = s.col; }
+            icfg->aggs[j].kind = FWA_COUNT;
+            icfg->aggs[j].col = 0;
+            if (!read[s.col]) icfg->nullable_cols &= ~(1 << s.col);   // nothing else reads its NULL flags
+        }
+        return FWA_OK;
+    }
     if (u->size_ms > 0 && u->size_ms < kDistMinSize) return no("windows shorter than 64 ms are not supported");
     // value-column indices: a source column that only COUNT(DISTINCT) reads hands its index to its marked column;
     // otherwise the marked column takes an index nothing else uses
@@ -324,10 +551,11 @@ int dist_plan(const fwa_config* u, DistinctPlan* P, fwa_config* icfg, std::strin
 void dist_free(DistinctPlan* P) {
     if (!P) return;
     for (void* p : {(void*)P->d_tab, (void*)P->d_mark, (void*)P->d_stage, (void*)P->d_ctr, (void*)P->d_side, (void*)P->d_bcnt,
-                    (void*)P->d_bpre})
+                    (void*)P->d_bpre, (void*)P->d_rtab, (void*)P->d_wins})
         if (p) (void)hipFree(p);
     if (P->h_ctr) (void)hipHostFree(P->h_ctr);
     for (hipEvent_t ev : P->ev) if (ev) (void)hipEventDestroy(ev);
+    for (hipEvent_t ev : P->rev) if (ev) (void)hipEventDestroy(ev);
     delete P;
 }
 
@@ -343,6 +571,19 @@ int64_t dist_qmin(const fwa_engine* e) {
     };
     const int64_t lw = e->tz.empty() ? e->wm : jm::tz_to_local(e->tz.data(), (int)(e->tz.size() / 2), e->wm);
     int64_t q = slice_q(e, lw);
+    if (e->dist && e->dist->range) {
+        // a window of many slices: "fired" only ever turns off as q grows (the last window's end does not decrease), so
+        // the first unfired slice of (q - slices per window - 66, q + 2] comes from a bisection; outside that: unknown
+        const int64_t back = e->size / e->g + 66;
+        if (q > LONG_MAX_J - 4 || q < LONG_MIN_J + back + 4) return LONG_MIN_J;
+        int64_t lo = q - back, hi = q + 2;                    // fired(lo), !fired(hi)
+        if (!fired(lo) || fired(hi)) return LONG_MIN_J;
+        while (hi - lo > 1) {
+            const int64_t mid = lo + (hi - lo) / 2;
+            if (fired(mid)) lo = mid; else hi = mid;
+        }
+        return hi;
+    }
     if (q > LONG_MAX_J - 2 || q < LONG_MIN_J + 70) return LONG_MIN_J;
     q += 1;
     for (int step = 0; step < 64; ++step, --q) if (fired(q - 1)) return q;
@@ -359,8 +600,13 @@ int dist_counters(fwa_engine* e) {
     HIPCHK(e, hipMalloc(&P->d_bcnt, sizeof(unsigned int) * kDistScanGrid));
     HIPCHK(e, hipMalloc(&P->d_bpre, sizeof(unsigned long long) * kDistScanGrid));
     for (hipEvent_t& ev : P->ev) HIPCHK(e, hipEventCreate(&ev));
+    if (P->range) for (hipEvent_t& ev : P->rev) HIPCHK(e, hipEventCreate(&ev));
     return FWA_OK;
 }
+
+// The live cut in the unit of the tag's slice field: q_min itself, or its block in range mode (a block is live while
+// its highest slice is).
+int64_t dist_cut(const DistinctPlan* P, int64_t q_min) { return P->range && q_min != LONG_MIN_J ? q_min >> 6 : q_min; }
 
 // Read ctr[0] (and check ctr[1]) after the work enqueued so far; synchronises.
 int dist_read_counter(fwa_engine* e, int64_t* out) {
@@ -396,22 +642,30 @@ int dist_compact(fwa_engine* e, int64_t q_min, int grid, int64_t livee) {
         P->d_side = nullptr;
         P->side_cap = 0;
         const int64_t cap = std::max<int64_t>(livee + livee / 4, 1 << 12);
-        HIPCHK(e, hipMalloc(&P->d_side, 24 * (size_t)cap));
+        HIPCHK(e, hipMalloc(&P->d_side, (P->range ? 32 : 24) * (size_t)cap));
         P->side_cap = cap;
     }
     int64_t taken = 0, moved = 0;
     HIPCHK(e, hipMemsetAsync(P->d_ctr, 0, 8, e->stream));
     distinct_prefix_kernel<<<1, 64, 0, e->stream>>>(P->d_bcnt, grid, P->d_bpre);
     HIPCHK(e, hipGetLastError());
-    distinct_extract_kernel<<<grid, 256, 0, e->stream>>>(P->d_tab, P->slots, q_min, P->d_side, P->side_cap, P->d_bpre,
-                                                         P->d_ctr);
+    if (P->range)
+        distinct_extract_kernel<true><<<grid, 256, 0, e->stream>>>(P->d_tab, P->slots, q_min, P->d_side, P->side_cap,
+                                                                   P->d_bpre, P->d_ctr);
+    else
+        distinct_extract_kernel<false><<<grid, 256, 0, e->stream>>>(P->d_tab, P->slots, q_min, P->d_side, P->side_cap,
+                                                                    P->d_bpre, P->d_ctr);
     HIPCHK(e, hipGetLastError());
     if (int rc = dist_read_counter(e, &taken)) return rc;
     if (taken != livee) return fail(e, FWA_E_STATE, "COUNT(DISTINCT) rebuild lost entries");
     if (taken > 0) {
         HIPCHK(e, hipMemsetAsync(P->d_ctr, 0, 8, e->stream));
-        distinct_insert_side_kernel<<<grid_for(taken, 4096), 256, 0, e->stream>>>(P->d_side, P->side_cap, taken, P->d_tab,
-                                                                                  (uint64_t)P->slots - 1, P->d_ctr);
+        if (P->range)
+            distinct_insert_side_kernel<true><<<grid_for(taken, 4096), 256, 0, e->stream>>>(
+                P->d_side, P->side_cap, taken, P->d_tab, (uint64_t)P->slots - 1, P->d_ctr);
+        else
+            distinct_insert_side_kernel<false><<<grid_for(taken, 4096), 256, 0, e->stream>>>(
+                P->d_side, P->side_cap, taken, P->d_tab, (uint64_t)P->slots - 1, P->d_ctr);
         HIPCHK(e, hipGetLastError());
         if (int rc = dist_read_counter(e, &moved)) return rc;
         if (moved != livee) return fail(e, FWA_E_STATE, "COUNT(DISTINCT) rebuild lost entries");
@@ -438,7 +692,7 @@ int dist_reserve(fwa_engine* e, int64_t add) {
         P->last_add = 0;
     }
     if (P->bound + add <= P->slots / 2) { P->bound += add; return FWA_OK; }
-    const int64_t q_min = dist_qmin(e);
+    const int64_t q_min = dist_cut(P, dist_qmin(e));          // (range mode: the cut is a block number)
     const int grid = grid_for(P->slots, kDistScanGrid);
     int64_t livee = 0;
     if (int rc = dist_count_live(e, q_min, grid, &livee)) return rc;
@@ -453,7 +707,12 @@ int dist_reserve(fwa_engine* e, int64_t add) {
     hipError_t r = hipMemsetAsync(ntab, 0, 32 * (size_t)nslots, e->stream);
     if (r == hipSuccess) r = hipMemsetAsync(P->d_ctr, 0, 8, e->stream);
     if (r == hipSuccess) {
-        distinct_rebuild_kernel<<<grid, 256, 0, e->stream>>>(P->d_tab, P->slots, q_min, ntab, (uint64_t)nslots - 1, P->d_ctr);
+        if (P->range)
+            distinct_rebuild_kernel<true><<<grid, 256, 0, e->stream>>>(P->d_tab, P->slots, q_min, ntab,
+                                                                       (uint64_t)nslots - 1, P->d_ctr);
+        else
+            distinct_rebuild_kernel<false><<<grid, 256, 0, e->stream>>>(P->d_tab, P->slots, q_min, ntab,
+                                                                        (uint64_t)nslots - 1, P->d_ctr);
         r = hipGetLastError();
     }
     int64_t moved = 0;
@@ -529,7 +788,7 @@ int dist_mark(fwa_engine* e, const int64_t** keys, const int64_t** ts, const voi
         }
         HIPCHK(e, err);
     }
-    if (n > P->mark_cap) {
+    if (!P->range && n > P->mark_cap) {
         if (P->d_mark) HIPCHK(e, hipFree(P->d_mark));
         P->d_mark = nullptr;
         P->mark_cap = 0;
@@ -551,11 +810,12 @@ int dist_mark(fwa_engine* e, const int64_t** keys, const int64_t** ts, const voi
     for (int d = 0; d < P->nd; ++d) {
         a.src[d] = (const int64_t*)vals[P->src[d]];
         a.nul[d] = nulls[P->src[d]];
-        a.mark[d] = P->d_mark + (size_t)d * (size_t)P->mark_cap;
+        a.mark[d] = P->range ? nullptr : P->d_mark + (size_t)d * (size_t)P->mark_cap;
     }
     HIPCHK(e, hipMemsetAsync(P->d_ctr + 2, 0, 8, e->stream));
     HIPCHK(e, hipEventRecord(P->ev[0], e->stream));
-    distinct_mark_kernel<<<grid_for(n, 1 << 16), 256, 0, e->stream>>>(a, e->d_ec);
+    if (P->range) distinct_mark_range_kernel<<<grid_for(n, 1 << 16), 256, 0, e->stream>>>(a, e->d_ec);
+    else distinct_mark_kernel<<<grid_for(n, 1 << 16), 256, 0, e->stream>>>(a, e->d_ec);
     HIPCHK(e, hipGetLastError());
     HIPCHK(e, hipEventRecord(P->ev[1], e->stream));
     P->timing = true;
@@ -570,8 +830,81 @@ int dist_mark(fwa_engine* e, const int64_t** keys, const int64_t** ts, const voi
             other |= u.aggs[j].kind != FWA_COUNT && u.aggs[j].kind != FWA_COUNT_DISTINCT && u.aggs[j].col == P->src[d];
         if (!other) vals[P->src[d]] = nullptr;
     }
-    for (int d = 0; d < P->nd; ++d) vals[P->mcol[d]] = a.mark[d];
+    for (int d = 0; d < P->nd && !P->range; ++d) vals[P->mcol[d]] = a.mark[d];
     for (int c = 0; c < FWA_MAX_COLS; ++c) if (!((e->cfg.nullable_cols >> c) & 1)) nulls[c] = nullptr;
+    return FWA_OK;
+}
+
+// Range mode: the distinct columns of the rows [row0, row0 + nrows) that a watermark step just fired for `wins`
+// ((end, start) as fwa_advance_watermark collects them; both fire paths emit these bounds unchanged). Enqueued on the
+// handle's stream behind the fire and ahead of anything a later push sets; synchronises before the rows are read.
+int dist_range_count(fwa_engine* e, const std::set<std::pair<int64_t, int64_t>>& wins, int64_t row0, int64_t nrows) {
+    DistinctPlan* P = e->dist;
+    if (nrows <= 0 || wins.empty()) return FWA_OK;
+    if (nrows >= (int64_t)1 << 31) return fail(e, FWA_E_STATE, "COUNT(DISTINCT): too many rows in one firing step");
+    if (int rc = dist_counters(e)) return rc;
+    std::vector<DistWin> hw;
+    hw.reserve(wins.size());
+    for (auto& w : wins) hw.push_back({slice_q(e, w.second), slice_q(e, jm::wsub(w.first, 1)), w.first});
+    if ((int64_t)hw.size() > P->wins_cap) {
+        if (P->d_wins) HIPCHK(e, hipFree(P->d_wins));
+        P->d_wins = nullptr;
+        P->wins_cap = 0;
+        const int64_t cap = std::max<int64_t>(2 * (int64_t)hw.size(), 64);
+        HIPCHK(e, hipMalloc(&P->d_wins, sizeof(DistWin) * (size_t)cap));
+        P->wins_cap = cap;
+    }
+    const int64_t rcap = dist_pow2(2 * nrows);
+    if (rcap > P->rtab_cap) {
+        if (P->d_rtab) HIPCHK(e, hipFree(P->d_rtab));
+        P->d_rtab = nullptr;
+        P->rtab_cap = 0;
+        HIPCHK(e, hipMalloc(&P->d_rtab, sizeof(unsigned int) * (size_t)rcap));
+        P->rtab_cap = rcap;
+    }
+    if (int rc = upload(e, P->d_wins, hw.data(), sizeof(DistWin) * hw.size())) return rc;
+    DistRangeArgs a;
+    memset(&a, 0, sizeof(a));
+    a.tab = P->d_tab;
+    a.slots = P->slots;
+    a.smask = (uint64_t)P->slots - 1;
+    a.wins = P->d_wins;
+    a.nw = (int32_t)hw.size();
+    a.o_key = e->o_key;
+    a.o_end = e->o_end;
+    a.row0 = row0;
+    a.nrows = nrows;
+    a.rtab = P->d_rtab;
+    a.rmask = (uint32_t)(rcap - 1);
+    a.ctr = P->d_ctr;
+    for (int j = 0; j < P->ucfg.num_aggs; ++j) {
+        if (!((P->mask >> j) & 1)) continue;
+        const int oj = e->dec ? e->dec->umap[j] : j;       // (a DECIMAL plan renumbers the internal aggregates)
+        if (oj < 0) return fail(e, FWA_E_STATE, "COUNT(DISTINCT) aggregate has no output column");
+        for (int d = 0; d < P->nd; ++d) if (P->src[d] == P->ucfg.aggs[j].col) a.agg_d[a.na] = d;
+        a.o_agg[a.na++] = (unsigned long long*)e->o_agg[oj];
+    }
+    HIPCHK(e, hipMemsetAsync(P->d_rtab, 0, sizeof(unsigned int) * (size_t)rcap, e->stream));
+    HIPCHK(e, hipMemsetAsync(P->d_ctr + 3, 0, 8, e->stream));
+    HIPCHK(e, hipEventRecord(P->rev[0], e->stream));
+    dist_rows_index_kernel<<<grid_for(nrows, (int64_t)1 << 23), 256, 0, e->stream>>>(a);
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, hipEventRecord(P->rev[1], e->stream));
+    if (P->d_tab) {   // (no table: nothing but NULLs was ever pushed, every count stays 0)
+        dist_range_count_kernel<<<grid_for(P->slots, kDistScanGrid), 256, 0, e->stream>>>(a);
+        HIPCHK(e, hipGetLastError());
+    }
+    HIPCHK(e, hipEventRecord(P->rev[2], e->stream));
+    HIPCHK(e, hipMemcpyAsync(P->h_ctr + 3, P->d_ctr + 3, 8, hipMemcpyDeviceToHost, e->stream));
+    if (int rc = stream_sync(e)) return rc;
+    if (P->h_ctr[3]) return fail(e, FWA_E_STATE, "COUNT(DISTINCT): a counted value's (key, window) has no fired row");
+    float ms0 = 0.f, ms1 = 0.f;
+    HIPCHK(e, hipEventElapsedTime(&ms0, P->rev[0], P->rev[1]));
+    HIPCHK(e, hipEventElapsedTime(&ms1, P->rev[1], P->rev[2]));
+    P->index_ms += ms0;
+    P->count_ms += ms1;
+    P->count_steps++;
+    e->fire_ms += ms0 + ms1;
     return FWA_OK;
 }
 
@@ -585,18 +918,39 @@ int dist_snapshot_section(fwa_engine* e, std::vector<int64_t>* sec, int64_t* m_o
     // host's memory are bounded by the live count, not by the table
     int64_t m = 0;
     std::vector<unsigned long long> w;
+    std::vector<int64_t> qs;                              // range mode: the slice number of entry i
     if (P->d_tab) {
         if (int rc = dist_counters(e)) return rc;
-        const int64_t q_min = dist_qmin(e);
+        const int64_t q_live = dist_qmin(e);
+        const int64_t q_min = dist_cut(P, q_live);
         const int grid = grid_for(P->slots, kDistScanGrid);
         if (int rc = dist_count_live(e, q_min, grid, &m)) return rc;
         if (int rc = dist_compact(e, q_min, grid, m)) return rc;
         P->bound = m;                                     // exact now: the pending estimate of the last push is void
         P->last_add = 0;
-        w.resize(3 * (size_t)m);
-        for (int c = 0; c < 3 && m > 0; ++c)
+        const int nw = P->range ? 4 : 3;
+        w.resize((size_t)nw * (size_t)m);
+        for (int c = 0; c < nw && m > 0; ++c)
             HIPCHK(e, hipMemcpy(w.data() + (size_t)c * m, P->d_side + (size_t)c * P->side_cap, 8 * (size_t)m,
                                 hipMemcpyDeviceToHost));
+        if (P->range) {
+            // one section entry per set bit of a live block, its slice's number in qs[]; the bits of slices under
+            // q_live belong to fired windows only and stay behind
+            std::vector<unsigned long long> x[3];
+            const int64_t mb = m;
+            for (int64_t i = 0; i < mb; ++i) {
+                const int64_t b0 = (int64_t)((uint64_t)dist_tag_q(w[2 * mb + i]) << 6);
+                for (unsigned long long bits = w[3 * mb + i]; bits; bits &= bits - 1) {
+                    const int64_t q = b0 + __builtin_ctzll(bits);
+                    if (q < q_live) continue;
+                    for (int c = 0; c < 3; ++c) x[c].push_back(w[(size_t)c * mb + i]);
+                    qs.push_back(q);
+                }
+            }
+            m = (int64_t)qs.size();
+            w.resize(3 * (size_t)m);
+            for (int c = 0; c < 3 && m > 0; ++c) memcpy(w.data() + (size_t)c * m, x[c].data(), 8 * (size_t)m);
+        }
     }
     std::vector<int32_t> kg((size_t)m);
     std::vector<int64_t> off((size_t)maxp + 1, 0);
@@ -617,7 +971,7 @@ int dist_snapshot_section(fwa_engine* e, std::vector<int64_t>* sec, int64_t* m_o
         const uint64_t t = w[2 * m + i];
         body[d] = (t & 8) ? 0 : (int64_t)w[i];
         body[m + d] = (t & 16) ? 0 : (int64_t)w[m + i];
-        body[2 * m + d] = slice_start(e, dist_tag_q(t));
+        body[2 * m + d] = slice_start(e, P->range ? qs[i] : dist_tag_q(t));
         body[3 * m + d] = (int64_t)(t & 7);
     }
     *m_out = m;
@@ -633,21 +987,29 @@ int dist_restore_section(fwa_engine* e, const int64_t* sec, int64_t m) {
     const int64_t n = hi - lo;
     if (n == 0) return FWA_OK;
     const int64_t* body = sec + maxp + 1;
-    std::vector<unsigned long long> w(3 * (size_t)n);
+    const size_t nw = P->range ? 4 : 3;                   // range mode: block tag + the slice's bit, folded by the insert
+    std::vector<unsigned long long> w(nw * (size_t)n);
     for (int64_t i = 0; i < n; ++i) {
         const uint64_t key = (uint64_t)body[lo + i], val = (uint64_t)body[m + lo + i];
         const int64_t d = body[3 * m + lo + i];
         if (d < 0 || d >= P->nd) return fail(e, FWA_E_ARG, "corrupt COUNT(DISTINCT) entry");
+        const int64_t q = slice_q(e, body[2 * m + lo + i]);
         w[i] = key ? key : 1ull;
         w[n + i] = val ? val : 1ull;
-        w[2 * n + i] = dist_tag(slice_q(e, body[2 * m + lo + i]), key, val, (int)d);
+        w[2 * n + i] = dist_tag(P->range ? q >> 6 : q, key, val, (int)d);
+        if (P->range) w[3 * n + i] = 1ull << (q & 63);
     }
     if (int rc = dist_reserve(e, n)) return rc;
     unsigned long long* dw = nullptr;
-    HIPCHK(e, hipMalloc(&dw, 24 * (size_t)n));
-    hipError_t r = hipMemcpyAsync(dw, w.data(), 24 * (size_t)n, hipMemcpyHostToDevice, e->stream);
+    HIPCHK(e, hipMalloc(&dw, 8 * nw * (size_t)n));
+    hipError_t r = hipMemcpyAsync(dw, w.data(), 8 * nw * (size_t)n, hipMemcpyHostToDevice, e->stream);
     if (r == hipSuccess) {
-        distinct_insert_side_kernel<<<grid_for(n), 256, 0, e->stream>>>(dw, n, n, P->d_tab, (uint64_t)P->slots - 1, P->d_ctr);
+        if (P->range)
+            distinct_insert_side_kernel<true><<<grid_for(n), 256, 0, e->stream>>>(dw, n, n, P->d_tab,
+                                                                                  (uint64_t)P->slots - 1, P->d_ctr);
+        else
+            distinct_insert_side_kernel<false><<<grid_for(n), 256, 0, e->stream>>>(dw, n, n, P->d_tab,
+                                                                                   (uint64_t)P->slots - 1, P->d_ctr);
         r = hipGetLastError();
     }
     const hipError_t rs = hipStreamSynchronize(e->stream);

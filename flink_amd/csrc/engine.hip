@@ -2445,7 +2445,8 @@ int validate(const fwa_config* c) {
         default:
             return FWA_E_ARG;
     }
-    if (c->flags & ~(FWA_CFG_DYNAMIC_GAP | FWA_CFG_LATE_INDICES | FWA_CFG_RECORD_LISTS | FWA_CFG_REDUCE | FWA_CFG_BY_LAST))
+    if (c->flags & ~(FWA_CFG_DYNAMIC_GAP | FWA_CFG_LATE_INDICES | FWA_CFG_RECORD_LISTS | FWA_CFG_REDUCE | FWA_CFG_BY_LAST |
+                     FWA_CFG_DISTINCT_RANGE))
         return FWA_E_ARG;
     {   // DataStream built-in reductions (include/flink_amd.h FWA_CFG_REDUCE)
         int nby = 0, nsel = 0, nfirst = 0, nred = 0, nother = 0;
@@ -5781,6 +5782,12 @@ int fwa_advance_watermark(fwa_engine* e, int64_t wm, fwa_out* out) {
             int rc = launch_fire(e, hw, hs, 0, &nrows, e->late_rows, wm);
             if (rc) return rc;
         }
+        // COUNT(DISTINCT) over HOP / CUMULATE: the step's rows are final, their distinct columns come from the set
+        // now -- behind the fire, ahead of the next push's bits, before the slices retire (distinct.inc)
+        if (e->dist && e->dist->range && !spec_done) {
+            int rcd = dist_range_count(e, wins, 0, nrows);
+            if (rcd) return rcd;
+        }
         int rc = retire_slices(e, wm);
         if (rc) return rc;
         e->wm = wm;
@@ -5948,6 +5955,7 @@ int fwa_set_option(fwa_engine* e, int32_t option, int64_t value) {
             e->dist->first_slots = value;
             return FWA_OK;
         case FWA_OPT_DISTINCT_LIVE: case FWA_OPT_DISTINCT_REBUILDS: case FWA_OPT_STRAGGLERS: case FWA_OPT_KEY_TABLE_DIGEST:
+        case FWA_OPT_DISTINCT_INDEX_US: case FWA_OPT_DISTINCT_COUNT_US: case FWA_OPT_DISTINCT_COUNT_STEPS:
             return fail(e, FWA_E_ARG, "read-only option");
         default: return fail(e, FWA_E_ARG, "unknown option");
     }
@@ -5991,6 +5999,11 @@ int fwa_get_option(const fwa_engine* e, int32_t option, int64_t* value) {
             if (!e->dist) return FWA_E_UNSUPPORTED;
             *value = option == FWA_OPT_DISTINCT_SLOTS ? (e->dist->slots ? e->dist->slots : e->dist->first_slots)
                    : option == FWA_OPT_DISTINCT_LIVE ? e->dist->live : e->dist->rebuilds;
+            return FWA_OK;
+        case FWA_OPT_DISTINCT_INDEX_US: case FWA_OPT_DISTINCT_COUNT_US: case FWA_OPT_DISTINCT_COUNT_STEPS:
+            if (!e->dist || !e->dist->range) return FWA_E_UNSUPPORTED;
+            *value = option == FWA_OPT_DISTINCT_COUNT_STEPS ? e->dist->count_steps
+                   : (int64_t)(1000.0 * (option == FWA_OPT_DISTINCT_INDEX_US ? e->dist->index_ms : e->dist->count_ms));
             return FWA_OK;
         default: return FWA_E_ARG;
     }

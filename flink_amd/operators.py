@@ -173,6 +173,10 @@ class SlicingWindowProcessor(_Base):
         kw.setdefault("track_late", True)
         self.spec = spec
         self.tz = kw.get("tz")
+        # COUNT(DISTINCT) over hopping / cumulative windows is counted from the set at the fire (FWA_CFG_DISTINCT_RANGE):
+        # the facade decides for its caller, as a planner shim would
+        if spec.window_kind in ("SLIDE", "CUMULATE") and any(a[0] == "COUNT_DISTINCT" for a in aggs):
+            kw.setdefault("distinct_range", True)
         super().__init__(spec, aggs, **kw)
 
     def process_element(self, key, row_values, rowtime):

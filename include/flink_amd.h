@@ -132,8 +132,8 @@ enum fwa_agg_kind {
  * JAVA_LONG, BINROW_BIGINT and GROUP_PREFIXED, any offset, a shift time zone, nullable columns, FWA_CFG_LATE_INDICES,
  * FWA_CFG_RECORD_LISTS (forced or auto-selected). FWA_E_UNSUPPORTED (fwa_last_error names COUNT(DISTINCT); for a
  * refused fwa_create, fwa_last_error(NULL) on the calling thread):
- *   FWA_SLIDE, FWA_CUMULATE, FWA_SESSION -- a window of several slices needs the union of the per-slice sets, which is
- *     not additive;
+ *   FWA_SLIDE, FWA_CUMULATE without FWA_CFG_DISTINCT_RANGE (below), FWA_SESSION -- a window of several slices needs the
+ *     union of the per-slice sets, which is not additive;
  *   FWA_SEM_DATASTREAM, FWA_CFG_REDUCE, FWA_KEY_PREHASHED -- the engine snapshot needs each entry's key group and no
  *     hash is kept per set entry;
  *   fwa_drain_partials, fwa_push_partials, fwa_drain_route, fwa_fire_partials -- a distinct count is not mergeable
@@ -147,7 +147,15 @@ enum fwa_agg_kind {
  * them 0 times. Like the reference operator after an exception in processElement, such a handle is to be destroyed
  * and restored from its last snapshot, not retried.
  * size_ms >= 64 is a deliberate limit of this build: a smaller slice number could be kept whole only by a fourth
- * CAS word per entry or by a host check of every push's slice range; the 64 ms bound costs neither. */
+ * CAS word per entry or by a host check of every push's slice range; the 64 ms bound costs neither.
+ * Range mode (FWA_CFG_DISTINCT_RANGE on a Table FWA_SLIDE or FWA_CUMULATE handle): the reference merges the MapViews
+ * of a window's slices at the fire (SliceSharedWindowAggProcessor, DistinctInfo); here the set keeps one entry per
+ * (key, value, column, block of 64 consecutive slices) with a 64-bit bitmap of the slices the value occurred in, the
+ * push only sets bits (no marked column), and every firing step of fwa_advance_watermark runs one pass over the set
+ * that counts, per fired window, the values with a bit inside the window's slice range. That pass is the cost the flag
+ * opts into; the TUMBLE form pays nothing at the fire. The 64 ms minimum does not apply in range mode (the entry keeps
+ * the block number, six bits fewer than the slice number). Aggregates, NULLs, time zones, snapshots (one section
+ * entry per set bit, the layout below) and the remaining refusals are as above; record lists are TUMBLE-only. */
 /* Built-in DataStream reductions (FWA_CFG_REDUCE): WindowedStream.sum / min / max / minBy / maxBy(pos)
  * (WindowedStream.java:680-890) reduce the window's elements in arrival order with SumAggregator
  * (SumAggregator.java:66-76) or ComparableAggregator (ComparableAggregator.java:83-107): the result is a copy of the
@@ -277,6 +285,9 @@ typedef struct fwa_config {
                                   * Selected automatically when key_capacity >= 2^25; fwa_get_config reports it.
                                   * Same results, snapshots and partials as the dense layout. Other configurations:
                                   * FWA_E_UNSUPPORTED. */
+#define FWA_CFG_DISTINCT_RANGE 0x20 /* Table HOP / CUMULATE: allow FWA_COUNT_DISTINCT; the count of a window is taken
+                                     * from the set at the fire (a pass over the live entries per firing step). No
+                                     * effect on a TUMBLE handle (the marked-column path runs as without the flag). */
 
 typedef struct fwa_out {
     int64_t n_rows;
@@ -577,13 +588,18 @@ enum fwa_option {
     FWA_OPT_DISTINCT_SLOTS = 18, /* COUNT(DISTINCT): first size of the set in slots (a power of two >= 64, before the
                                     first push; default: sized from the first push); tests force growth with it.
                                     fwa_get_option: the current size */
-    FWA_OPT_DISTINCT_LIVE = 19,  /* read only: set entries of unfired windows counted at the last rebuild */
+    FWA_OPT_DISTINCT_LIVE = 19,  /* read only: set entries of unfired windows counted at the last rebuild (range mode,
+                                    FWA_CFG_DISTINCT_RANGE: entries are per block of 64 slices, so this counts blocks) */
     FWA_OPT_DISTINCT_REBUILDS = 20, /* read only: rebuilds of the set (growth, dropping fired windows' entries, and one
                                       per fwa_snapshot, which reads the live entries out of a rebuild) */
     FWA_OPT_STRAGGLERS = 21,     /* read only: bucket entries of the two-phase pushes so far that were older than their
                                     combiner block's slice window and were applied after its last merge (fwa_get_option) */
-    FWA_OPT_KEY_TABLE_DIGEST = 22 /* read only: FNV-1a digest of the key table's words in slot order (fwa_get_option;
+    FWA_OPT_KEY_TABLE_DIGEST = 22,/* read only: FNV-1a digest of the key table's words in slot order (fwa_get_option;
                                      diagnostic: equal for two handles that placed every key in the same slot) */
+    FWA_OPT_DISTINCT_INDEX_US = 23, /* read only, FWA_CFG_DISTINCT_RANGE: device microseconds the firing steps so far spent
+                                       indexing their rows (also part of fwa_stats.fire_ms) */
+    FWA_OPT_DISTINCT_COUNT_US = 24, /* read only, FWA_CFG_DISTINCT_RANGE: ... and scanning the set for the counts */
+    FWA_OPT_DISTINCT_COUNT_STEPS = 25 /* read only, FWA_CFG_DISTINCT_RANGE: firing steps counted so far */
 };
 int fwa_set_option(fwa_engine* e, int32_t option, int64_t value);
 /* The option's effective value: for the tri-state options 1 if the handle currently takes that path (forced, or
