@@ -209,7 +209,17 @@ enum fwa_agg_kind {
  * MinAggFunction.java:63-, AvgAggFunction.java:65-106: AVG = sum / count of non-NULL inputs); COUNT(*) counts
  * rows, COUNT(col) non-NULL values. SUM(FLOAT) is accumulated in double and rounded to float once at the
  * fire (the reference keeps a float buffer: the results differ by at most that buffer's own rounding,
- * n * 2^-24 * sum|x| for n inputs). */
+ * n * 2^-24 * sum|x| for n inputs). That bound holds only while the reference's float buffer stays finite: where it
+ * overflowed ([3e38, 3e38, -3e38] is Inf in float order) the engine returns the rounded double sum (3e38). */
+/* Special float values on handles without FWA_CFG_REDUCE (for reduce handles see above). MIN / MAX order their inputs
+ * (FLOAT widened to double first) by their bits: -0.0 is below 0.0, a NaN with a clear sign bit is above +Inf and a
+ * NaN with a set sign bit below -Inf, whatever the arrival order. The reference's result in those cases depends on
+ * arrival order (its fold is first || v < x: [0.0, -0.0] has MIN 0.0 but [-0.0, 0.0] has MAX -0.0; [NaN, 1.0] has MIN
+ * NaN but [1.0, NaN, 2.0] has MIN 1.0); the engine's result is always one the reference can produce for some order of
+ * the same values -- NaN only if the window holds one, else the extreme of the other values, a zero of either sign
+ * only when both occur. SUM starts from +0.0, so a window of only
+ * -0.0 sums to +0.0 (the reference keeps -0.0); a NaN input, or +Inf together with -Inf, gives NaN, one infinity
+ * alone gives itself. */
 
 enum fwa_status {
     FWA_OK = 0,
