@@ -31,6 +31,12 @@ AGG_KINDS = {
     "MINBY_F32": 29, "MAXBY_F32": 30, "SEL_64": 31, "SEL_32": 32,
     "COUNT_DISTINCT": 33,    # COUNT(DISTINCT col): 8-byte values compared by their bits (Table TUMBLE)
 }
+# FWA_AGG_DISTINCT: the DISTINCT modifier bit of fwa_agg_spec.kind, accepted on SUM / AVG over BIGINT and DOUBLE
+AGG_DISTINCT = 0x100
+DISTINCT_SUM_KINDS = {"SUM_DISTINCT_I64": "SUM_I64", "SUM_DISTINCT_F64": "SUM_F64",
+                      "AVG_DISTINCT_I64": "AVG_I64", "AVG_DISTINCT_F64": "AVG_F64"}
+AGG_KINDS.update({name: AGG_DISTINCT | AGG_KINDS[base] for name, base in DISTINCT_SUM_KINDS.items()})
+DISTINCT_KINDS = ("COUNT_DISTINCT",) + tuple(DISTINCT_SUM_KINDS)
 DEC_KINDS = ("SUM_DEC", "AVG_DEC", "SUM_DEC128", "AVG_DEC128")
 AGG_NAMES = {v: k for k, v in AGG_KINDS.items()}
 # numpy dtype of each aggregate's RESULT column
@@ -45,6 +51,7 @@ AGG_RESULT_DTYPE = {
     "MINBY_I64": "i8", "MAXBY_I64": "i8", "MINBY_I32": "i4", "MAXBY_I32": "i4", "MINBY_F64": "f8", "MAXBY_F64": "f8",
     "MINBY_F32": "f4", "MAXBY_F32": "f4", "SEL_64": "i8", "SEL_32": "i4",
     "COUNT_DISTINCT": "i8",
+    "SUM_DISTINCT_I64": "i8", "SUM_DISTINCT_F64": "f8", "AVG_DISTINCT_I64": "i8", "AVG_DISTINCT_F64": "f8",
 }
 # numpy dtype of each aggregate's INPUT column (None: no input)
 AGG_INPUT_DTYPE = {
@@ -56,6 +63,7 @@ AGG_INPUT_DTYPE = {
     "MINBY_I64": "i8", "MAXBY_I64": "i8", "MINBY_I32": "i4", "MAXBY_I32": "i4", "MINBY_F64": "f8", "MAXBY_F64": "f8",
     "MINBY_F32": "f4", "MAXBY_F32": "f4", "SEL_64": "i8", "SEL_32": "i4",
     "COUNT_DISTINCT": "i8",
+    "SUM_DISTINCT_I64": "i8", "SUM_DISTINCT_F64": "f8", "AVG_DISTINCT_I64": "i8", "AVG_DISTINCT_F64": "f8",
 }
 
 
@@ -169,8 +177,8 @@ def make_config(window_kind="TUMBLE", semantics="DATASTREAM", size_ms=10_000, sl
     per-record session gaps (DynamicEventTimeSessionWindows). tz: [(utc_instant_ms, offset_ms), ...] shift
     time zone of a TIMESTAMP_LTZ rowtime (the struct keeps a pointer to a buffer held on the struct). reduce: a
     DataStream built-in reduction (FWA_CFG_REDUCE, WindowedStream.sum/min/max/minBy/maxBy); by_last: minBy / maxBy
-    ties go to the last element (FWA_CFG_BY_LAST). distinct_range: allow COUNT_DISTINCT on a Table HOP / CUMULATE
-    handle, counted from the set at every fire (FWA_CFG_DISTINCT_RANGE)."""
+    ties go to the last element (FWA_CFG_BY_LAST). distinct_range: allow COUNT_DISTINCT and SUM / AVG_DISTINCT_* on a
+    Table HOP / CUMULATE handle, taken from the set at every fire (FWA_CFG_DISTINCT_RANGE)."""
     c = Config()
     c.abi_version = FWA_ABI_VERSION
     c.window_kind = WINDOW_KINDS[window_kind] if isinstance(window_kind, str) else int(window_kind)

@@ -1,4 +1,5 @@
-// COUNT(DISTINCT col) over Table TUMBLE windows (include/flink_amd.h, FWA_COUNT_DISTINCT) -- included by engine.hip.
+// COUNT / SUM / AVG(DISTINCT col) over Table windows (include/flink_amd.h, FWA_COUNT_DISTINCT, FWA_AGG_DISTINCT) --
+// included by engine.hip.
 //
 // Reference: the planner expands COUNT(DISTINCT c) into a distinct view (a MapView<value, bitmap> per (key, slice) in
 // the accumulator, DistinctInfo / AggsHandlerCodeGenerator.addReusableDistinctAccumulators) and counts a value the first
@@ -60,6 +61,14 @@
 // A live entry without a row is a broken invariant (accepted record => COUNT(*) > 0 => a row): the step fails.
 // Rebuilds carry word 3 (the live cut is the block of q_min: a block is live while its highest slice is); the snapshot
 // section keeps its layout, one entry per set bit, and restore folds them back.
+//
+// SUM / AVG(DISTINCT col) (FWA_AGG_DISTINCT on SUM_I64 / SUM_F64 / AVG_I64 / AVG_F64). The entry's word 1 already is the
+// value, so the sum rides on the count. TUMBLE: distinct_mark_kernel<true> also writes w = mark ? value : 0 per summed
+// column (bits 0: the identity of the BIGINT and of the DOUBLE sum), dist_plan rewrites the aggregate in place into
+// SUM_I64(w) / SUM_F64(w), and the distinct count SUM_I64(m) -- the caller's COUNT_DISTINCT or a hidden aggregate behind
+// the caller's -- decides NULL and divides AVG. Range mode: dist_range_count_kernel<true> adds the decoded value and 1
+// to two plan-owned per-row columns where it counts an entry. Either way dist_finish_kernel writes the caller-visible
+// value and NULL flag into plan-owned columns at fill_out (never in place: fill_out may run twice over the same rows).
 
 struct DistWin { int64_t q_lo, q_hi, end; };   // a fired window: its slice range and its end as the fire emits it
 
@@ -68,12 +77,28 @@ struct DistinctPlan {
     int32_t nd = 0;                        // marked columns (one per distinct source column)
     int32_t src[FWA_MAX_AGGS] = {};        // marked column d: the caller's value column
     int32_t mcol[FWA_MAX_AGGS] = {};       // ... and the internal value-column index of its 0/1 column
-    int64_t mask = 0;                      // bit j: the caller's aggregate j is COUNT_DISTINCT (snapshot header)
+    int64_t mask = 0;                      // bit j: the caller's aggregate j is a distinct one (snapshot header)
+    int64_t cmask = 0;                     // ... and of those, the COUNT_DISTINCT ones
+    // SUM / AVG(DISTINCT) (FWA_AGG_DISTINCT): the sum beside the count, finished into plan-owned columns (dist_finish)
+    int32_t ns = 0;                        // summed source columns
+    int32_t sidx[FWA_MAX_AGGS] = {};       // marked column d: its ordinal among the summed ones, -1: only counted
+    int32_t sf64[FWA_MAX_AGGS] = {};       // ... its values are DOUBLE bits (else BIGINT)
+    int32_t wcol[FWA_MAX_AGGS] = {};       // ... TUMBLE: the internal value-column index of w = mark ? value : 0
+    int32_t fkind[FWA_MAX_AGGS] = {};      // caller's aggregate j: FWA_SUM_I64 / SUM_F64 / AVG_I64 / AVG_F64 when it
+                                           // carries FWA_AGG_DISTINCT, else 0
+    int32_t fd[FWA_MAX_AGGS] = {};         // ... its marked column
+    int32_t fsum[FWA_MAX_AGGS] = {};       // ... TUMBLE: the internal aggregate summing w
+    int32_t fcnt[FWA_MAX_AGGS] = {};       // ... TUMBLE: the internal aggregate summing m (the distinct count)
+    unsigned long long* d_fout[FWA_MAX_AGGS] = {};   // finished results and NULL flags per such aggregate, [fout_cap]
+    uint8_t* d_fnull[FWA_MAX_AGGS] = {};
+    int64_t fout_cap = 0;
+    unsigned long long* d_rsum = nullptr;  // range mode: per-row sums [ns][rs_cap], then per-row distinct counts [ns][rs_cap]
+    int64_t rs_cap = 0;
     unsigned long long* d_tab = nullptr;   // the set, [slots][4]
     int64_t slots = 0, first_slots = 0;    // first_slots: FWA_OPT_DISTINCT_SLOTS (0: sized from the first push)
     int64_t bound = 0;                     // upper bound of occupied slots
     int64_t live = 0, rebuilds = 0;        // entries counted at the last rebuild; rebuilds so far
-    unsigned long long* d_mark = nullptr;  // marked columns, [nd][mark_cap]
+    unsigned long long* d_mark = nullptr;  // marked columns, [nd][mark_cap], then the summed columns w, [ns][mark_cap]
     int64_t mark_cap = 0;
     char* d_stage = nullptr;               // host pushes: every input column, staged once
     size_t stage_bytes = 0;
@@ -172,6 +197,7 @@ struct DistMarkArgs {
     const int64_t* src[FWA_MAX_AGGS];      // source value column of marked column d (8-byte values, compared by bits)
     const uint8_t* nul[FWA_MAX_AGGS];      // its NULL flags (nullptr: none)
     unsigned long long* mark[FWA_MAX_AGGS];
+    unsigned long long* wsum[FWA_MAX_AGGS]; // SUM / AVG(DISTINCT): w = mark ? value : 0 (nullptr: column d is only counted)
     int32_t nd;
     int64_t n;
     int64_t q_min;                         // first slice whose window has not fired at the handle's watermark
@@ -181,6 +207,9 @@ struct DistMarkArgs {
 };
 
 // One thread per record: the slice number as the ingest kernels compute it, then one set insert per marked column.
+// S: some column is also summed -- its first occurrences carry their value into w (bits 0 are the identity of both the
+// BIGINT and the DOUBLE sum, +0.0); the count-only instantiation has neither the store nor the pointer loads.
+template <bool S>
 __global__ void __launch_bounds__(256) distinct_mark_kernel(DistMarkArgs a, const EngineConst* __restrict__ cp) {
     const EngineConst& c = *cp;
     unsigned int created = 0;
@@ -188,15 +217,17 @@ __global__ void __launch_bounds__(256) distinct_mark_kernel(DistMarkArgs a, cons
         const uint64_t key = (uint64_t)a.keys[i];
         const int64_t q = sp_slice(c, assign_ts(c, a.ts[i]));
         for (int d = 0; d < a.nd; ++d) {
-            unsigned long long m = 0ull;
+            unsigned long long m = 0ull, w = 0ull;
             if (q >= a.q_min && !(a.nul[d] && a.nul[d][i])) {
                 const uint64_t v = (uint64_t)a.src[d][i];
                 const int r = dist_insert(a.tab, a.smask, key ? key : 1ull, v ? v : 1ull, dist_tag(q, key, v, d));
                 if (r < 0) atomicAdd(a.ctr + 1, 1ull);
                 m = r > 0 ? 1ull : 0ull;
+                if (S) w = r > 0 ? v : 0ull;
                 created += r > 0 ? 1u : 0u;
             }
             a.mark[d][i] = m;
+            if (S) { if (a.wsum[d]) a.wsum[d][i] = w; }
         }
     }
     for (int o = 32; o > 0; o >>= 1) created += __shfl_down(created, o);    // the whole wave is back here
@@ -383,6 +414,11 @@ struct DistRangeArgs {
     uint32_t rmask;                        // row-table slots - 1
     unsigned long long* o_agg[FWA_MAX_AGGS];   // output column of distinct aggregate a
     int32_t agg_d[FWA_MAX_AGGS];               // ... and the ordinal of its source column
+    int32_t ns;                                // summed source columns (SUM / AVG(DISTINCT))
+    int32_t sum_d[FWA_MAX_AGGS];               // ... their ordinals among the source columns
+    int32_t sum_f64[FWA_MAX_AGGS];             // ... DOUBLE bits (else BIGINT)
+    unsigned long long* r_sum[FWA_MAX_AGGS];   // ... per-row sum of the window's distinct values (plan-owned)
+    unsigned long long* r_cnt[FWA_MAX_AGGS];   // ... and their number
     unsigned long long* ctr;
 };
 
@@ -397,6 +433,7 @@ __global__ void __launch_bounds__(256) dist_rows_index_kernel(DistRangeArgs a) {
     if (i >= a.nrows) return;
     const int64_t row = a.row0 + i;
     for (int j = 0; j < a.na; ++j) a.o_agg[j][row] = 0ull;
+    for (int s = 0; s < a.ns; ++s) { a.r_sum[s][row] = 0ull; a.r_cnt[s][row] = 0ull; }   // (0: +0.0 as well)
     uint32_t h = dist_row_hash(a.o_key[row], a.o_end[row]) & a.rmask;
     for (uint32_t probe = 0; probe <= a.rmask; ++probe, h = (h + 1) & a.rmask)
         if (atomicCAS(a.rtab + h, 0u, (unsigned int)(i + 1)) == 0u) return;
@@ -420,7 +457,11 @@ __device__ __forceinline__ int64_t dist_row_find(const DistRangeArgs& a, int64_t
 // block of its (key, value, d) iff no earlier block B' in [q_lo >> 6, B) holds an entry with bits in the range -- one
 // read-only probe per earlier block, none for a window inside one block. Only the first block counts: +1 on the row of
 // (key, window end) for every aggregate over column d. Entries without a row are counted in ctr[3] (one atomic per wave).
+// S: some column is also summed -- where the entry counts, its decoded value (a stored 1 with tag bit 4 is 0) is added
+// to the row's sum of column d (u64 add: BIGINT wraps by itself; DOUBLE: a double atomic add) and 1 to the row's
+// distinct count of d, which the finish step needs even without a COUNT_DISTINCT of the caller's.
 constexpr int kDistWinLds = 128;
+template <bool S>
 __global__ void __launch_bounds__(256) dist_range_count_kernel(DistRangeArgs a) {
     __shared__ DistWin s_win[kDistWinLds];
     int64_t lo, hi;
@@ -451,6 +492,15 @@ __global__ void __launch_bounds__(256) dist_range_count_kernel(DistRangeArgs a) 
                 if (row < 0) { ++miss; continue; }
                 const int d = (int)(tb.x & 7ull);
                 for (int j = 0; j < a.na; ++j) if (a.agg_d[j] == d) atomicAdd(a.o_agg[j] + row, 1ull);
+                if (S) {
+                    const unsigned long long v = (tb.x & 16ull) ? 0ull : kv.y;
+                    for (int s = 0; s < a.ns; ++s) {
+                        if (a.sum_d[s] != d) continue;
+                        if (a.sum_f64[s]) atomicAdd(reinterpret_cast<double*>(a.r_sum[s] + row), __longlong_as_double((long long)v));
+                        else atomicAdd(a.r_sum[s] + row, v);
+                        atomicAdd(a.r_cnt[s] + row, 1ull);
+                    }
+                }
             }
         }
     }
@@ -458,23 +508,81 @@ __global__ void __launch_bounds__(256) dist_range_count_kernel(DistRangeArgs a) 
     if ((threadIdx.x & 63) == 0 && miss) atomicAdd(a.ctr + 3, (unsigned long long)miss);
 }
 
+// ---- SUM / AVG(DISTINCT): the finish of the fired rows ----
+
+struct DistFinDesc {
+    const unsigned long long* sum;         // per row: the sum of the window's distinct values (BIGINT or DOUBLE bits)
+    const unsigned long long* cnt;         // ... and their number
+    unsigned long long* out;               // the caller-visible column (plan-owned: the inputs stay as fired)
+    uint8_t* nul;
+    int32_t kind;                          // FWA_SUM_I64 / SUM_F64 / AVG_I64 / AVG_F64
+};
+struct DistFinArgs {
+    DistFinDesc a[FWA_MAX_AGGS];
+    int32_t na;
+    int64_t n;
+};
+
+// One thread per (row, aggregate): SQL NULL without a non-NULL value; AVG(BIGINT) divides like Java's long division
+// (truncating; the divisor is a positive count), AVG(DOUBLE) by the count as a double.
+__global__ void __launch_bounds__(256) dist_finish_kernel(DistFinArgs f) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= f.n) return;
+    const DistFinDesc& d = f.a[blockIdx.y];
+    const unsigned long long c = d.cnt[i];
+    unsigned long long r = c ? d.sum[i] : 0ull;
+    if (c && d.kind == FWA_AVG_I64) r = (unsigned long long)((long long)r / (long long)c);
+    else if (c && d.kind == FWA_AVG_F64)
+        r = (unsigned long long)__double_as_longlong(__longlong_as_double((long long)r) / (double)(long long)c);
+    d.out[i] = r;
+    d.nul[i] = c ? 0 : 1;
+}
+
 // ---- host ----
 
+// FWA_AGG_DISTINCT on a kind (SUM / AVG(DISTINCT col)); dist_plan refuses the bit on every kind it does not belong to
+bool dist_is_sum(int kind) { return kind > 0 && (kind & FWA_AGG_DISTINCT) != 0; }
+bool dist_is_kind(int kind) { return kind == FWA_COUNT_DISTINCT || dist_is_sum(kind); }
+
 bool has_distinct(const fwa_config* c) {
-    for (int j = 0; j < c->num_aggs && j < FWA_MAX_AGGS; ++j) if (c->aggs[j].kind == FWA_COUNT_DISTINCT) return true;
+    for (int j = 0; j < c->num_aggs && j < FWA_MAX_AGGS; ++j) if (dist_is_kind(c->aggs[j].kind)) return true;
     return false;
 }
 
-// The internal configuration of a handle with COUNT(DISTINCT) aggregates: each one rewritten in place into SUM_I64 of
-// its marked column (same position, same result type: no output remapping). 0 or an fwa_status with *why set.
+// The internal configuration of a handle with distinct aggregates. COUNT_DISTINCT(c) is rewritten in place into
+// SUM_I64 of the marked column m of c (same position, same result type). SUM / AVG(DISTINCT c) (FWA_AGG_DISTINCT) is
+// rewritten in place into SUM_I64 / SUM_F64 of a second engine-written column w = mark ? value : 0 (the two forms over
+// one column share that accumulator) and finished at the fire from it and from the distinct count SUM_I64(m): the
+// caller's own COUNT_DISTINCT(c), or a hidden aggregate appended behind the caller's, so caller positions never move.
+// Range mode rewrites every distinct aggregate into a COUNT(*) placeholder. 0 or an fwa_status with *why set.
 int dist_plan(const fwa_config* u, DistinctPlan* P, fwa_config* icfg, std::string* why) {
     P->ucfg = *u;
     *icfg = *u;
     if (u->num_aggs < 0 || u->num_aggs > FWA_MAX_AGGS) return FWA_E_ARG;
+    int base[FWA_MAX_AGGS] = {};                              // the kind without the modifier bit
+    int vtype[FWA_MAX_COLS] = {};                             // summed source column: 1 BIGINT, 2 DOUBLE
     for (int j = 0; j < u->num_aggs; ++j) {
         const fwa_agg_spec& s = u->aggs[j];
-        if (s.kind < 0 || s.kind >= FWA_AGG_KIND_COUNT) return FWA_E_ARG;
-        if (s.kind != FWA_COUNT && (s.col < 0 || s.col >= FWA_MAX_COLS)) return FWA_E_ARG;
+        base[j] = dist_is_sum(s.kind) ? (s.kind & ~FWA_AGG_DISTINCT) : s.kind;
+        if (base[j] < 0 || base[j] >= FWA_AGG_KIND_COUNT) return FWA_E_ARG;
+        if (base[j] != FWA_COUNT && (s.col < 0 || s.col >= FWA_MAX_COLS)) return FWA_E_ARG;
+        if (!dist_is_sum(s.kind)) continue;
+        const bool i64 = base[j] == FWA_SUM_I64 || base[j] == FWA_AVG_I64;
+        const bool f64 = base[j] == FWA_SUM_F64 || base[j] == FWA_AVG_F64;
+        if (!i64 && !f64) {
+            const bool named = base[j] == FWA_SUM_F32 || base[j] == FWA_AVG_F32 || base[j] == FWA_SUM_I32 ||
+                               (base[j] >= FWA_SUM_DEC && base[j] <= FWA_AVG_DEC128);
+            *why = named ? "FWA_AGG_DISTINCT: FLOAT, INT and DECIMAL distinct sums are not supported (SUM / AVG(DISTINCT) "
+                           "over BIGINT and DOUBLE only)"
+                         : "FWA_AGG_DISTINCT: a modifier of FWA_SUM_I64, FWA_SUM_F64, FWA_AVG_I64 and FWA_AVG_F64 only "
+                           "(MIN / MAX(DISTINCT) are plain MIN / MAX, COUNT(DISTINCT) is FWA_COUNT_DISTINCT)";
+            return FWA_E_ARG;
+        }
+        if (vtype[s.col] && vtype[s.col] != (i64 ? 1 : 2)) {
+            *why = "FWA_AGG_DISTINCT: BIGINT and DOUBLE distinct aggregates over one value column";
+            return FWA_E_ARG;
+        }
+        vtype[s.col] = i64 ? 1 : 2;
     }
     auto no = [&](const char* m) { *why = std::string("COUNT(DISTINCT): ") + m; return FWA_E_UNSUPPORTED; };
     const bool hop = u->window_kind == FWA_SLIDE || u->window_kind == FWA_CUMULATE;
@@ -488,21 +596,31 @@ int dist_plan(const fwa_config* u, DistinctPlan* P, fwa_config* icfg, std::strin
     if (u->flags & FWA_CFG_REDUCE) return no("not a DataStream reduction");
     if (u->key_kind == FWA_KEY_PREHASHED)
         return no("PREHASHED keys are not supported (the set keeps no hash per entry to place it in a key group)");
+    // the marked column of aggregate j's source column (created on first use), and what SUM / AVG(DISTINCT) adds to it
+    auto column_of = [&](int j) {
+        const fwa_agg_spec& s = u->aggs[j];
+        int d = -1;
+        for (int i = 0; i < P->nd; ++i) if (P->src[i] == s.col) d = i;
+        if (d < 0) { d = P->nd++; P->src[d] = s.col; P->sidx[d] = -1; }
+        P->mask |= (int64_t)1 << j;
+        if (!dist_is_sum(s.kind)) { P->cmask |= (int64_t)1 << j; return d; }
+        if (P->sidx[d] < 0) { P->sidx[d] = P->ns++; P->sf64[d] = vtype[s.col] == 2; }
+        P->fkind[j] = base[j];
+        P->fd[j] = d;
+        return d;
+    };
     if (hop) {
-        // range mode: COUNT_DISTINCT(c) -> COUNT(*), a BIGINT that is never NULL, shares column 0 and reads no value
+        // range mode: a distinct aggregate -> COUNT(*), a BIGINT that is never NULL, shares column 0 and reads no value
         // column, so nothing is remapped and the handle keeps the two-phase ingest and the carried HOP sums; the fire
-        // overwrites the column from the set (dist_range_count)
+        // overwrites the column from the set (dist_range_count), sums go to plan-owned columns
         P->range = true;
         bool read[FWA_MAX_COLS] = {};
         for (int j = 0; j < u->num_aggs; ++j)
-            if (u->aggs[j].kind != FWA_COUNT && u->aggs[j].kind != FWA_COUNT_DISTINCT) read[u->aggs[j].col] = true;
+            if (u->aggs[j].kind != FWA_COUNT && !dist_is_kind(u->aggs[j].kind)) read[u->aggs[j].col] = true;
         for (int j = 0; j < u->num_aggs; ++j) {
             const fwa_agg_spec& s = u->aggs[j];
-            if (s.kind != FWA_COUNT_DISTINCT) continue;
-            P->mask |= (int64_t)1 << j;
-            int d = -1;
-            for (int i = 0; i < P->nd; ++i) if (P->src[i] == s.col) d = i;
-            if (d < 0) { d = P->nd++; P->src[d] = s.col; }
+            if (!dist_is_kind(s.kind)) continue;
+            column_of(j);
             icfg->aggs[j].kind = FWA_COUNT;
             icfg->aggs[j].col = 0;
             if (!read[s.col]) icfg->nullable_cols &= ~(1 << s.col);   // nothing else reads its NULL flags
@@ -510,16 +628,16 @@ int dist_plan(const fwa_config* u, DistinctPlan* P, fwa_config* icfg, std::strin
         return FWA_OK;
     }
     if (u->size_ms > 0 && u->size_ms < kDistMinSize) return no("windows shorter than 64 ms are not supported");
-    // value-column indices: a source column that only COUNT(DISTINCT) reads hands its index to its marked column;
-    // otherwise the marked column takes an index nothing else uses
+    // value-column indices: a source column that only distinct aggregates read hands its index to its marked column;
+    // otherwise the marked column takes an index nothing else uses, and so does every summed column w
     bool used[FWA_MAX_COLS] = {}, isrc[FWA_MAX_COLS] = {};
     for (int j = 0; j < u->num_aggs; ++j) {
         const fwa_agg_spec& s = u->aggs[j];
-        if (s.kind == FWA_COUNT_DISTINCT) isrc[s.col] = true;
+        if (dist_is_kind(s.kind)) isrc[s.col] = true;
         else if (s.kind != FWA_COUNT) used[s.col] = true;     // COUNT(col) reads the column's NULL flags
     }
-    int mof[FWA_MAX_COLS];
-    for (int c = 0; c < FWA_MAX_COLS; ++c) mof[c] = -1;
+    int mof[FWA_MAX_COLS], wof[FWA_MAX_COLS];
+    for (int c = 0; c < FWA_MAX_COLS; ++c) mof[c] = wof[c] = -1;
     for (int c = 0; c < FWA_MAX_COLS; ++c) if (isrc[c] && !used[c]) mof[c] = c;
     for (int c = 0; c < FWA_MAX_COLS; ++c) {
         if (!isrc[c] || mof[c] >= 0) continue;
@@ -530,29 +648,58 @@ int dist_plan(const fwa_config* u, DistinctPlan* P, fwa_config* icfg, std::strin
         }
         if (mof[c] < 0) return no("no free value column for the marked column (FWA_MAX_COLS)");
     }
+    for (int c = 0; c < FWA_MAX_COLS; ++c) {
+        if (!vtype[c]) continue;
+        for (int m = 0; m < FWA_MAX_COLS && wof[c] < 0; ++m) {
+            if (used[m] || isrc[m]) continue;
+            wof[c] = m;
+            used[m] = true;
+        }
+        if (wof[c] < 0) return no("no free value column for the summed column of SUM / AVG(DISTINCT) (FWA_MAX_COLS)");
+    }
+    int cnt_of[FWA_MAX_AGGS];                                 // marked column d: the internal aggregate SUM_I64(m)
+    for (int d = 0; d < FWA_MAX_AGGS; ++d) cnt_of[d] = -1;
     for (int j = 0; j < u->num_aggs; ++j) {
         const fwa_agg_spec& s = u->aggs[j];
-        if (s.kind != FWA_COUNT_DISTINCT) continue;
-        P->mask |= (int64_t)1 << j;
-        int d = -1;
-        for (int i = 0; i < P->nd; ++i) if (P->src[i] == s.col) d = i;
-        if (d < 0) {
-            d = P->nd++;
-            P->src[d] = s.col;
-            P->mcol[d] = mof[s.col];
-        }
-        icfg->aggs[j].kind = FWA_SUM_I64;
-        icfg->aggs[j].col = P->mcol[d];
+        if (!dist_is_kind(s.kind)) continue;
+        const int d = column_of(j);
+        P->mcol[d] = mof[s.col];
         icfg->nullable_cols &= ~(1 << P->mcol[d]);            // the marked column holds no NULLs
+        if (!dist_is_sum(s.kind)) {
+            icfg->aggs[j].kind = FWA_SUM_I64;
+            icfg->aggs[j].col = P->mcol[d];
+            if (cnt_of[d] < 0) cnt_of[d] = j;
+            continue;
+        }
+        P->wcol[d] = wof[s.col];
+        icfg->nullable_cols &= ~(1 << P->wcol[d]);            // nor does w: a NULL or repeated value is the identity
+        icfg->aggs[j].kind = P->sf64[d] ? FWA_SUM_F64 : FWA_SUM_I64;
+        icfg->aggs[j].col = P->wcol[d];
+        P->fsum[j] = j;
     }
+    for (int d = 0; d < P->nd; ++d) {                         // the hidden counters, behind the caller's aggregates
+        if (P->sidx[d] < 0 || cnt_of[d] >= 0) continue;
+        if (icfg->num_aggs >= FWA_MAX_AGGS)
+            return no("SUM / AVG(DISTINCT) needs one more aggregate for the hidden distinct count of its column, and "
+                      "none of the FWA_MAX_AGGS is left");
+        cnt_of[d] = icfg->num_aggs;
+        icfg->aggs[icfg->num_aggs].kind = FWA_SUM_I64;
+        icfg->aggs[icfg->num_aggs].col = P->mcol[d];
+        icfg->num_aggs++;
+    }
+    for (int j = 0; j < u->num_aggs; ++j) if (P->fkind[j]) P->fcnt[j] = cnt_of[P->fd[j]];
     return FWA_OK;
 }
 
 void dist_free(DistinctPlan* P) {
     if (!P) return;
     for (void* p : {(void*)P->d_tab, (void*)P->d_mark, (void*)P->d_stage, (void*)P->d_ctr, (void*)P->d_side, (void*)P->d_bcnt,
-                    (void*)P->d_bpre, (void*)P->d_rtab, (void*)P->d_wins})
+                    (void*)P->d_bpre, (void*)P->d_rtab, (void*)P->d_wins, (void*)P->d_rsum})
         if (p) (void)hipFree(p);
+    for (int j = 0; j < FWA_MAX_AGGS; ++j) {
+        if (P->d_fout[j]) (void)hipFree(P->d_fout[j]);
+        if (P->d_fnull[j]) (void)hipFree(P->d_fnull[j]);
+    }
     if (P->h_ctr) (void)hipHostFree(P->h_ctr);
     for (hipEvent_t ev : P->ev) if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : P->rev) if (ev) (void)hipEventDestroy(ev);
@@ -793,7 +940,7 @@ int dist_mark(fwa_engine* e, const int64_t** keys, const int64_t** ts, const voi
         P->d_mark = nullptr;
         P->mark_cap = 0;
         const int64_t cap = std::max<int64_t>(n, 1 << 16);
-        HIPCHK(e, hipMalloc(&P->d_mark, sizeof(unsigned long long) * (size_t)cap * (size_t)P->nd));
+        HIPCHK(e, hipMalloc(&P->d_mark, sizeof(unsigned long long) * (size_t)cap * (size_t)(P->nd + P->ns)));
         P->mark_cap = cap;
     }
     if (int rc = dist_reserve(e, n * P->nd)) return rc;
@@ -811,26 +958,31 @@ int dist_mark(fwa_engine* e, const int64_t** keys, const int64_t** ts, const voi
         a.src[d] = (const int64_t*)vals[P->src[d]];
         a.nul[d] = nulls[P->src[d]];
         a.mark[d] = P->range ? nullptr : P->d_mark + (size_t)d * (size_t)P->mark_cap;
+        a.wsum[d] = P->range || P->sidx[d] < 0 ? nullptr : P->d_mark + (size_t)(P->nd + P->sidx[d]) * (size_t)P->mark_cap;
     }
     HIPCHK(e, hipMemsetAsync(P->d_ctr + 2, 0, 8, e->stream));
     HIPCHK(e, hipEventRecord(P->ev[0], e->stream));
     if (P->range) distinct_mark_range_kernel<<<grid_for(n, 1 << 16), 256, 0, e->stream>>>(a, e->d_ec);
-    else distinct_mark_kernel<<<grid_for(n, 1 << 16), 256, 0, e->stream>>>(a, e->d_ec);
+    else if (P->ns) distinct_mark_kernel<true><<<grid_for(n, 1 << 16), 256, 0, e->stream>>>(a, e->d_ec);
+    else distinct_mark_kernel<false><<<grid_for(n, 1 << 16), 256, 0, e->stream>>>(a, e->d_ec);
     HIPCHK(e, hipGetLastError());
     HIPCHK(e, hipEventRecord(P->ev[1], e->stream));
     P->timing = true;
     HIPCHK(e, hipMemcpyAsync(P->h_ctr + 2, P->d_ctr + 2, 8, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(e, hipEventRecord(P->ev[2], e->stream));
     P->last_add = n * P->nd;
-    // the internal layout: a source column that only COUNT(DISTINCT) read is not passed on (its index may now hold
+    // the internal layout: a source column that only distinct aggregates read is not passed on (its index may now hold
     // its marked column, or a DECIMAL piece); NULL flags only where the internal configuration still declares them
     for (int d = 0; d < P->nd; ++d) {
         bool other = false;
         for (int j = 0; j < u.num_aggs; ++j)
-            other |= u.aggs[j].kind != FWA_COUNT && u.aggs[j].kind != FWA_COUNT_DISTINCT && u.aggs[j].col == P->src[d];
+            other |= u.aggs[j].kind != FWA_COUNT && !dist_is_kind(u.aggs[j].kind) && u.aggs[j].col == P->src[d];
         if (!other) vals[P->src[d]] = nullptr;
     }
-    for (int d = 0; d < P->nd && !P->range; ++d) vals[P->mcol[d]] = a.mark[d];
+    for (int d = 0; d < P->nd && !P->range; ++d) {
+        vals[P->mcol[d]] = a.mark[d];
+        if (a.wsum[d]) vals[P->wcol[d]] = a.wsum[d];
+    }
     for (int c = 0; c < FWA_MAX_COLS; ++c) if (!((e->cfg.nullable_cols >> c) & 1)) nulls[c] = nullptr;
     return FWA_OK;
 }
@@ -853,6 +1005,14 @@ int dist_range_count(fwa_engine* e, const std::set<std::pair<int64_t, int64_t>>&
         const int64_t cap = std::max<int64_t>(2 * (int64_t)hw.size(), 64);
         HIPCHK(e, hipMalloc(&P->d_wins, sizeof(DistWin) * (size_t)cap));
         P->wins_cap = cap;
+    }
+    if (P->ns && row0 + nrows > P->rs_cap) {
+        if (P->d_rsum) HIPCHK(e, hipFree(P->d_rsum));
+        P->d_rsum = nullptr;
+        P->rs_cap = 0;
+        const int64_t cap = std::max<int64_t>(row0 + nrows + nrows / 4, 1 << 12);
+        HIPCHK(e, hipMalloc(&P->d_rsum, 16 * (size_t)cap * (size_t)P->ns));
+        P->rs_cap = cap;
     }
     const int64_t rcap = dist_pow2(2 * nrows);
     if (rcap > P->rtab_cap) {
@@ -878,12 +1038,21 @@ int dist_range_count(fwa_engine* e, const std::set<std::pair<int64_t, int64_t>>&
     a.rmask = (uint32_t)(rcap - 1);
     a.ctr = P->d_ctr;
     for (int j = 0; j < P->ucfg.num_aggs; ++j) {
-        if (!((P->mask >> j) & 1)) continue;
+        if (!((P->cmask >> j) & 1)) continue;
         const int oj = e->dec ? e->dec->umap[j] : j;       // (a DECIMAL plan renumbers the internal aggregates)
         if (oj < 0) return fail(e, FWA_E_STATE, "COUNT(DISTINCT) aggregate has no output column");
         for (int d = 0; d < P->nd; ++d) if (P->src[d] == P->ucfg.aggs[j].col) a.agg_d[a.na] = d;
         a.o_agg[a.na++] = (unsigned long long*)e->o_agg[oj];
     }
+    for (int d = 0; d < P->nd; ++d) {
+        if (P->sidx[d] < 0) continue;
+        const int s = P->sidx[d];
+        a.sum_d[s] = d;
+        a.sum_f64[s] = P->sf64[d];
+        a.r_sum[s] = P->d_rsum + (size_t)s * (size_t)P->rs_cap;
+        a.r_cnt[s] = P->d_rsum + (size_t)(P->ns + s) * (size_t)P->rs_cap;
+    }
+    a.ns = P->ns;
     HIPCHK(e, hipMemsetAsync(P->d_rtab, 0, sizeof(unsigned int) * (size_t)rcap, e->stream));
     HIPCHK(e, hipMemsetAsync(P->d_ctr + 3, 0, 8, e->stream));
     HIPCHK(e, hipEventRecord(P->rev[0], e->stream));
@@ -891,7 +1060,8 @@ int dist_range_count(fwa_engine* e, const std::set<std::pair<int64_t, int64_t>>&
     HIPCHK(e, hipGetLastError());
     HIPCHK(e, hipEventRecord(P->rev[1], e->stream));
     if (P->d_tab) {   // (no table: nothing but NULLs was ever pushed, every count stays 0)
-        dist_range_count_kernel<<<grid_for(P->slots, kDistScanGrid), 256, 0, e->stream>>>(a);
+        if (P->ns) dist_range_count_kernel<true><<<grid_for(P->slots, kDistScanGrid), 256, 0, e->stream>>>(a);
+        else dist_range_count_kernel<false><<<grid_for(P->slots, kDistScanGrid), 256, 0, e->stream>>>(a);
         HIPCHK(e, hipGetLastError());
     }
     HIPCHK(e, hipEventRecord(P->rev[2], e->stream));
@@ -905,6 +1075,54 @@ int dist_range_count(fwa_engine* e, const std::set<std::pair<int64_t, int64_t>>&
     P->count_ms += ms1;
     P->count_steps++;
     e->fire_ms += ms0 + ms1;
+    return FWA_OK;
+}
+
+// SUM / AVG(DISTINCT): the caller-visible columns of the nrows fired rows into P->d_fout / d_fnull, from the internal
+// sums as fired (TUMBLE: the accumulators of w and m; range mode: the per-row columns of the step's count pass). The
+// inputs are left as they are, so fill_out may run again over the same rows. Synchronises.
+int dist_finish(fwa_engine* e, int64_t nrows) {
+    DistinctPlan* P = e->dist;
+    if (!P->ns) return FWA_OK;
+    if (nrows > P->fout_cap || !P->fout_cap) {
+        const int64_t cap = std::max<int64_t>(nrows + nrows / 4, 1 << 12);
+        for (int j = 0; j < P->ucfg.num_aggs; ++j) {
+            if (!P->fkind[j]) continue;
+            if (P->d_fout[j]) HIPCHK(e, hipFree(P->d_fout[j]));
+            if (P->d_fnull[j]) HIPCHK(e, hipFree(P->d_fnull[j]));
+            P->d_fout[j] = nullptr;
+            P->d_fnull[j] = nullptr;
+            HIPCHK(e, hipMalloc(&P->d_fout[j], 8 * (size_t)cap));
+            HIPCHK(e, hipMalloc(&P->d_fnull[j], (size_t)cap));
+        }
+        P->fout_cap = cap;
+    }
+    if (nrows == 0) return FWA_OK;
+    if (P->range && nrows > P->rs_cap) return fail(e, FWA_E_STATE, "SUM(DISTINCT): fired rows without a count pass");
+    DistFinArgs f;
+    memset(&f, 0, sizeof(f));
+    f.n = nrows;
+    for (int j = 0; j < P->ucfg.num_aggs; ++j) {
+        if (!P->fkind[j]) continue;
+        DistFinDesc& d = f.a[f.na++];
+        if (P->range) {
+            const int s = P->sidx[P->fd[j]];
+            d.sum = P->d_rsum + (size_t)s * (size_t)P->rs_cap;
+            d.cnt = P->d_rsum + (size_t)(P->ns + s) * (size_t)P->rs_cap;
+        } else {                                           // (a DECIMAL plan renumbers the internal aggregates)
+            const int is = e->dec ? e->dec->umap[P->fsum[j]] : P->fsum[j];
+            const int ic = e->dec ? e->dec->umap[P->fcnt[j]] : P->fcnt[j];
+            if (is < 0 || ic < 0) return fail(e, FWA_E_STATE, "SUM(DISTINCT) aggregate has no output column");
+            d.sum = (const unsigned long long*)e->o_agg[is];
+            d.cnt = (const unsigned long long*)e->o_agg[ic];
+        }
+        d.out = P->d_fout[j];
+        d.nul = P->d_fnull[j];
+        d.kind = P->fkind[j];
+    }
+    dist_finish_kernel<<<dim3((unsigned)((nrows + 255) / 256), (unsigned)f.na), 256, 0, e->stream>>>(f);
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, hipStreamSynchronize(e->stream));
     return FWA_OK;
 }
 

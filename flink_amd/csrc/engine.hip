@@ -2906,7 +2906,8 @@ int fwa_create(const fwa_config* ucfg, fwa_engine** out) {
     memset(&uc, 0, sizeof(uc));
     memcpy(&uc, ucfg, ucfg->abi_version == 3 ? offsetof(fwa_config, dec_scale) : sizeof(fwa_config));
     g_create_err.clear();
-    // COUNT(DISTINCT) -> SUM(BIGINT) of a marked column (distinct.inc), before the DECIMAL plan so the two compose
+    // COUNT / SUM / AVG(DISTINCT) -> sums of engine-written columns (distinct.inc), before the DECIMAL plan so the two
+    // compose; the FWA_AGG_DISTINCT bit is gone from the kinds after the rewrite, so validate never sees it
     DistinctPlan* D = nullptr;
     if (has_distinct(&uc)) {
         D = new DistinctPlan();
@@ -5157,7 +5158,7 @@ static void snap_header(const fwa_engine* e, int64_t* h, int64_t n) {
     h[24] = e->cfg.nullable_cols;
     h[25] = e->ec.naggs - e->ec.nout;
     for (int j = 0; j < e->cfg.num_aggs; ++j) h[26] |= (int64_t)(e->cfg.aggs[j].col & 15) << (4 * j);
-    h[27] = e->dist ? e->dist->mask : 0;   // the caller's aggregates that are COUNT(DISTINCT); h[28]: their set's entries
+    h[27] = e->dist ? e->dist->mask : 0;   // the caller's distinct aggregates (COUNT_DISTINCT, FWA_AGG_DISTINCT); h[28]: their set's entries
 }
 
 // Sessions: the blob's entries are the in-flight sessions (key, start, count, acc_j..., end) bucketed by
@@ -5659,7 +5660,8 @@ static int fill_out(fwa_engine* e, int64_t nrows, fwa_out* out) {
     memset(out, 0, sizeof(*out));
     out->n_rows = nrows;
     // the caller's aggregates: DECIMAL ones finished from their piece sums (decimal.inc), the others as fired
-    const int na = e->dec ? e->dec->ucfg.num_aggs : e->cfg.num_aggs;
+    // (a SUM / AVG(DISTINCT) plan may have appended hidden counters behind the caller's aggregates: they never show)
+    const int na = e->dist ? e->dist->ucfg.num_aggs : e->dec ? e->dec->ucfg.num_aggs : e->cfg.num_aggs;
     const void* col[FWA_MAX_AGGS];
     const uint8_t* nul[FWA_MAX_AGGS];
     size_t width[FWA_MAX_AGGS];
@@ -5674,6 +5676,11 @@ static int fill_out(fwa_engine* e, int64_t nrows, fwa_out* out) {
         }
     } else {
         for (int j = 0; j < na; ++j) { col[j] = e->o_agg[j]; nul[j] = e->o_null[j]; width[j] = type_size(e->cfg.aggs[j].kind); }
+    }
+    if (e->dist && e->dist->ns) {   // SUM / AVG(DISTINCT): finished from the sum and the distinct count (distinct.inc)
+        if (int rc = dist_finish(e, nrows)) return rc;
+        for (int j = 0; j < na; ++j)
+            if (e->dist->fkind[j]) { col[j] = e->dist->d_fout[j]; nul[j] = e->dist->d_fnull[j]; width[j] = 8; }
     }
     out->num_aggs = na;
     if (e->cfg.output_on_device) {

@@ -296,7 +296,8 @@ const char* kUnsupported = "heap layout: DataStream TUMBLE / SLIDE / SESSION agg
 const char* kNoDistinct = "heap layout of COUNT(DISTINCT): the set of values (MapView bytes in the reference) is not "
                           "written; fwa_snapshot / fwa_restore carry it";
 const char* why_unsupported(const fwa_config& c) {
-    for (int j = 0; j < c.num_aggs; ++j) if (c.aggs[j].kind == FWA_COUNT_DISTINCT) return kNoDistinct;
+    for (int j = 0; j < c.num_aggs; ++j)                               // (FWA_AGG_DISTINCT: SUM / AVG(DISTINCT), same view)
+        if (c.aggs[j].kind == FWA_COUNT_DISTINCT || (c.aggs[j].kind & FWA_AGG_DISTINCT)) return kNoDistinct;
     return kUnsupported;
 }
 

@@ -173,9 +173,9 @@ class SlicingWindowProcessor(_Base):
         kw.setdefault("track_late", True)
         self.spec = spec
         self.tz = kw.get("tz")
-        # COUNT(DISTINCT) over hopping / cumulative windows is counted from the set at the fire (FWA_CFG_DISTINCT_RANGE):
-        # the facade decides for its caller, as a planner shim would
-        if spec.window_kind in ("SLIDE", "CUMULATE") and any(a[0] == "COUNT_DISTINCT" for a in aggs):
+        # COUNT / SUM / AVG(DISTINCT) over hopping / cumulative windows are taken from the set at the fire
+        # (FWA_CFG_DISTINCT_RANGE): the facade decides for its caller, as a planner shim would
+        if spec.window_kind in ("SLIDE", "CUMULATE") and any(a[0] in A.DISTINCT_KINDS for a in aggs):
             kw.setdefault("distinct_range", True)
         super().__init__(spec, aggs, **kw)
 

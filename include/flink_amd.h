@@ -156,6 +156,31 @@ enum fwa_agg_kind {
  * opts into; the TUMBLE form pays nothing at the fire. The 64 ms minimum does not apply in range mode (the entry keeps
  * the block number, six bits fewer than the slice number). Aggregates, NULLs, time zones, snapshots (one section
  * entry per set bit, the layout below) and the remaining refusals are as above; record lists are TUMBLE-only. */
+/* SUM(DISTINCT col) and AVG(DISTINCT col): DISTINCT is a modifier bit OR-ed into fwa_agg_spec.kind, as it is a modifier
+ * in SQL (the planner's DistinctInfo: one distinct view per column, shared by every DISTINCT aggregate over it). */
+#define FWA_AGG_DISTINCT 0x100
+/* Accepted on FWA_SUM_I64, FWA_SUM_F64, FWA_AVG_I64 and FWA_AVG_F64 only; on any other kind (FWA_COUNT_DISTINCT and
+ * FWA_COUNT_COL included) fwa_create answers FWA_E_ARG. The enum, FWA_AGG_KIND_COUNT, every struct and the ABI version
+ * are unchanged: a caller that never sets the bit sees no difference. MIN / MAX(DISTINCT) are plain FWA_MIN_* / FWA_MAX_*
+ * (the planner drops the keyword), so nothing exists for them. FLOAT, INT and DECIMAL distinct sums are not supported
+ * (FWA_E_ARG; fwa_last_error(NULL) names them).
+ * Values are 8 bytes and equal iff their 64 bits are, the rule of FWA_COUNT_DISTINCT. BIGINT sums wrap in two's
+ * complement like FWA_SUM_I64; AVG(DISTINCT BIGINT) is sum / distinct count with Java's long division (truncating
+ * toward zero) like FWA_AVG_I64. DOUBLE sums follow FWA_SUM_F64: they start from +0.0, -0.0 and 0.0 are two values, a
+ * NaN (each NaN bit pattern is a value of its own), or +Inf together with -Inf, gives NaN; AVG(DISTINCT DOUBLE) is
+ * sum / (double) count. Two distinct aggregates of different value type over one column are FWA_E_ARG.
+ * NULL: the result of a (key, window) with no non-NULL value of col is SQL NULL; NULL inputs (fwa_push_nullable) are
+ * skipped. fwa_out.agg_null[j] is a real array for these aggregates even when col is not declared nullable.
+ * Accepted and refused exactly as FWA_COUNT_DISTINCT (above; the messages name COUNT(DISTINCT)): Table FWA_TUMBLE with
+ * size_ms >= 64, Table FWA_SLIDE / FWA_CUMULATE only under FWA_CFG_DISTINCT_RANGE, no PREHASHED keys, record lists on
+ * TUMBLE, shift time zones, FWA_CFG_LATE_INDICES, fwa_snapshot / fwa_restore with rescaling (snapshot header word 27
+ * has a bit for every distinct aggregate of either form; sums need no section of their own).
+ * TUMBLE: per summed column the marking pass writes a second engine-owned column w = first occurrence ? value : 0,
+ * which takes a value-column index nothing else uses (FWA_E_UNSUPPORTED when none of the FWA_MAX_COLS is free); SUM and
+ * AVG(DISTINCT) over one column share its sum. The distinct count that decides NULL and divides AVG is the caller's own
+ * FWA_COUNT_DISTINCT over the column, or else a hidden aggregate behind the caller's (FWA_E_UNSUPPORTED when the list
+ * then passes FWA_MAX_AGGS; caller positions never move, fwa_out.num_aggs is the caller's). Range mode: the fire's pass
+ * over the set adds each counted value to a per-row sum; no value column and no aggregate slot is used. */
 /* Built-in DataStream reductions (FWA_CFG_REDUCE): WindowedStream.sum / min / max / minBy / maxBy(pos)
  * (WindowedStream.java:680-890) reduce the window's elements in arrival order with SumAggregator
  * (SumAggregator.java:66-76) or ComparableAggregator (ComparableAggregator.java:83-107): the result is a copy of the

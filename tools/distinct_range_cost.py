@@ -4,9 +4,12 @@ of every push and the two passes of every firing step.
 Stream: the C3 stream of bench.py scaled down to a short run -- HOP 60 s / 1 s (Table), Zipf(1.1) keys over --keys
 items, 1e6 records per second of event time, bounded out-of-orderness 1 s, --batch records per push (2^24: 16.8 s of
 event time, so a step fires 16 or 17 windows), inputs in HBM, --warmup pushes then --pushes timed pushes, each followed
-by its watermark. Two handles over the same records, run one after the other, --repeats times alternating:
+by its watermark. Three handles over the same records (--kinds selects some), run one after the other, --repeats
+times alternating:
   sum       COUNT + SUM_I64(v)                                    (the same handle without the distinct aggregate)
   distinct  COUNT + COUNT_DISTINCT(v & 15) under the flag         (16 values per key)
+  distsum   distinct + SUM_DISTINCT_I64(v & 15)                   (FWA_AGG_DISTINCT: the count pass also adds each
+            counted value and 1 to two per-row columns, and a finish kernel writes the sum and its NULL flag)
 Numbers, per timed step (means over the timed steps of a run; every run is printed, so the spread is visible):
   step      push + watermark, host clock around calls that end in a device synchronise
   fire      fwa_stats.fire_ms (HIP events on the handle's stream; for the distinct handle it includes the two passes)
@@ -14,7 +17,8 @@ Numbers, per timed step (means over the timed steps of a run; every run is print
   index     FWA_OPT_DISTINCT_INDEX_US (dist_rows_index_kernel, HIP events)
   count     FWA_OPT_DISTINCT_COUNT_US (dist_range_count_kernel, HIP events)
 and the set's slots, live block entries and rebuilds at the end.
-Output: python tools/distinct_range_cost.py > profiles/<tag>_distinct_range_cost.txt"""
+Output: python tools/distinct_range_cost.py --kinds sum,distinct > profiles/<tag>_distinct_range_cost.txt
+        python tools/distinct_range_cost.py > profiles/<tag>_distinct_sum_range_cost.txt"""
 import argparse
 import os
 import sys
@@ -34,6 +38,7 @@ ap.add_argument("--warmup", type=int, default=2)
 ap.add_argument("--repeats", type=int, default=2)
 ap.add_argument("--batch", type=int, default=1 << 24)
 ap.add_argument("--keys", type=int, default=1_000_000)
+ap.add_argument("--kinds", default="sum,distinct,distsum")
 args = ap.parse_args()
 if not torch.cuda.is_available():
     sys.exit("distinct_range_cost.py measures on the GPU: none found")
@@ -58,6 +63,8 @@ wms = np.maximum.accumulate(bmax) - 1001
 
 def run(kind):
     aggs = [("COUNT", 0), ("SUM_I64", 0)] if kind == "sum" else [("COUNT", 0), ("COUNT_DISTINCT", 0)]
+    if kind == "distsum":
+        aggs.append(("SUM_DISTINCT_I64", 0))
     g = E.WindowAggregator(A.make_config(window_kind="SLIDE", semantics="TABLE", size_ms=60_000, slide_ms=1_000, aggs=aggs,
                                          key_capacity=args.keys, output_on_device=1, distinct_range=kind != "sum"))
     col = vals if kind == "sum" else dcol
@@ -94,5 +101,5 @@ def run(kind):
 print("C3-shaped stream, %d timed pushes of %d records after %d warm-up, %d Zipf(1.1) keys, HOP 60 s / 1 s (Table)"
       % (args.pushes, B, args.warmup, args.keys), flush=True)
 for _ in range(args.repeats):
-    for kind in ("sum", "distinct"):
+    for kind in args.kinds.split(","):
         run(kind)
