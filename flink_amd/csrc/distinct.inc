@@ -12,7 +12,8 @@
 // open-addressing set per handle and writes mark[i] = 1 iff this insert created the entry. Phase P / A, the fire
 // kernels, record lists and snapshots then see an ordinary 64-bit sum. A window of several slices (HOP, CUMULATE,
 // SESSION) needs the union of per-slice sets at the fire, which is not a sum: HOP and CUMULATE take it there under
-// FWA_CFG_DISTINCT_RANGE (range mode, below), everything else is refused.
+// FWA_CFG_DISTINCT_RANGE (range mode, below), Table SESSION windows of a fixed gap under FWA_CFG_DISTINCT_SESSION
+// (session mode, below); DataStream handles, reductions and PREHASHED keys are refused.
 //
 // The set. One 32-byte aligned entry per slot, three 64-bit words used (the fourth pads the entry to one 32-byte
 // sector, so a probe is one aligned vector load):
@@ -62,6 +63,23 @@
 // Rebuilds carry word 3 (the live cut is the block of q_min: a block is live while its highest slice is); the snapshot
 // section keeps its layout, one entry per set bit, and restore folds them back.
 //
+// Session mode (FWA_CFG_DISTINCT_SESSION on a Table SESSION handle: fixed gap g, no allowed lateness). The "slice" of a
+// record is its cell floor(local ts / g) (DESIGN.md section 2 has the argument): two accepted records of a key in one cell
+// are less than g apart and so in one session, two in-flight sessions of a key are more than g apart and so never share
+// a cell, and the session [s, e) holds exactly the key's accepted records of the cells [floor(s / g), floor((e - g) / g)].
+// The entry is the one of range mode with the cell in place of the slice (tag field = cell >> 6, word 3 = cell bitmap;
+// an entry is live iff its bitmap is non-zero). Two things differ from range mode, and both are needed for exactness:
+//   * the marking pass runs BEHIND the ingest and skips the records the ingest dropped (a dropped record may share its
+//     cell with an accepted one of another session: g = 10, watermark 20, 10 is dropped, 12 is accepted as [12, 22)).
+//     dist_plan makes the internal configuration collect the dropped indices on the device; dist_drop_mask_kernel
+//     scatters them into a byte mask and distinct_mark_session_kernel reads it.
+//   * a fired session's bits are cleared at its fire (g = 10: [0, 10) fires at watermark 9, then 5 is accepted as the
+//     new session [5, 15) in the same cell 0). dist_session_count: dist_sess_index_kernel enters every fired row once per
+//     64-cell block of its range in a (key, block) multimap, dist_sess_count_kernel<S> counts as the range count does
+//     (first block of the row's range that holds the value), dist_sess_clear_kernel -- a launch of its own, the count
+//     reads other entries' bits -- drops the bits inside each fired row's range. An entry that meets no fired row
+//     belongs to a session in flight.
+//
 // SUM / AVG(DISTINCT col) (FWA_AGG_DISTINCT on SUM_I64 / SUM_F64 / AVG_I64 / AVG_F64). The entry's word 1 already is the
 // value, so the sum rides on the count. TUMBLE: distinct_mark_kernel<true> also writes w = mark ? value : 0 per summed
 // column (bits 0: the identity of the BIGINT and of the DOUBLE sum), dist_plan rewrites the aggregate in place into
@@ -71,6 +89,13 @@
 // value and NULL flag into plan-owned columns at fill_out (never in place: fill_out may run twice over the same rows).
 
 struct DistWin { int64_t q_lo, q_hi, end; };   // a fired window: its slice range and its end as the fire emits it
+struct DistMarkHold {                      // session mode: what the marking pass behind the ingest reads
+    const int64_t* keys = nullptr;
+    const int64_t* ts = nullptr;
+    const int64_t* src[FWA_MAX_AGGS] = {};
+    const uint8_t* nul[FWA_MAX_AGGS] = {};
+    int64_t n = 0;                         // 0: nothing held
+};
 
 struct DistinctPlan {
     fwa_config ucfg;                       // the caller's configuration (fwa_get_config)
@@ -114,11 +139,20 @@ struct DistinctPlan {
     int64_t last_add = 0;                  // the last marking pass's share of `bound`, until its exact count replaces it
     // range mode (FWA_CFG_DISTINCT_RANGE, HOP / CUMULATE): word 3 is a slice bitmap, counts are taken at the fire
     bool range = false;
-    unsigned int* d_rtab = nullptr;        // the step's rows by (key, window end): row + 1 per slot, [rtab_cap]
+    // session mode (FWA_CFG_DISTINCT_SESSION): range is set too (same entry), the tag's field is cell >> 6
+    bool sess = false;
+    int64_t gap = 0;                       // the session gap = the cell width
+    uint8_t* d_dmask = nullptr;            // the push's dropped records as a byte mask, [dmask_cap]
+    int64_t dmask_cap = 0;
+    int64_t* d_rblk = nullptr;             // the block each slot of d_rtab was entered under, [rtab_cap]
+    int64_t rblk_cap = 0;
+    DistMarkHold hold;                     // the push's columns, kept from dist_mark to the pass behind the ingest
+    unsigned int* d_rtab = nullptr;        // the step's rows by (key, window end), session mode: by (key, block), once per
+                                           // block of the row's cell range: row + 1 per slot, [rtab_cap]
     int64_t rtab_cap = 0;
     DistWin* d_wins = nullptr;             // the step's windows, [wins_cap]
     int64_t wins_cap = 0;
-    hipEvent_t rev[3] = {};                // row-index pass begin, range-count pass begin / end
+    hipEvent_t rev[3] = {};                // row-index pass begin, count pass begin / end (session mode: the clear's end)
     double index_ms = 0.0, count_ms = 0.0; // their device time so far (also part of fire_ms)
     int64_t count_steps = 0;               // firing steps counted
 };
@@ -138,6 +172,11 @@ __host__ __device__ __forceinline__ uint64_t dist_tag(int64_t q, uint64_t key, u
     return ((uint64_t)q << 6) | 32ull | (val == 0 ? 16ull : 0ull) | (key == 0 ? 8ull : 0ull) | (uint64_t)(d & 7);
 }
 __host__ __device__ __forceinline__ int64_t dist_tag_q(uint64_t tag) { return (int64_t)tag >> 6; }
+// Session mode: the cell of a local timestamp, floor(t / g) with g > 0 (local time may be negative).
+__host__ __device__ __forceinline__ int64_t dist_cell(int64_t t, int64_t g) {
+    const int64_t q = t / g;
+    return (t < 0 && q * g != t) ? q - 1 : q;
+}
 
 // 1: this call created the entry, 0: it was there, -1: no slot (the host's bound makes that impossible); *slot: where
 __device__ __forceinline__ int dist_upsert(unsigned long long* tab, uint64_t smask, uint64_t k, uint64_t v, uint64_t t,
@@ -204,6 +243,8 @@ struct DistMarkArgs {
     unsigned long long* tab;
     uint64_t smask;                        // slots - 1
     unsigned long long* ctr;
+    const uint8_t* dmask;                  // session mode: 1 where the ingest dropped the record
+    int64_t gap;                           // ... and the cell width
 };
 
 // One thread per record: the slice number as the ingest kernels compute it, then one set insert per marked column.
@@ -263,6 +304,42 @@ __global__ void __launch_bounds__(256) distinct_mark_range_kernel(DistMarkArgs a
     if ((threadIdx.x & 63) == 0 && created) atomicAdd(a.ctr + 2, (unsigned long long)created);
 }
 
+// Session mode: the dropped-record indices of the push just ingested (list[0 .. *n), any order) as a byte mask over the
+// batch (zeroed ahead of the launch). *n is read on the device: the host never copies the list for this.
+__global__ void __launch_bounds__(256) dist_drop_mask_kernel(const int32_t* list, const unsigned long long* n, int64_t cap,
+                                                            uint8_t* mask) {
+    const int64_t m = (int64_t)*n < cap ? (int64_t)*n : cap;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t r = list[i];
+        if (r >= 0 && r < cap) mask[r] = 1;
+    }
+}
+
+// Session mode, one thread per record, behind the ingest: a record the ingest dropped sets no bit (its cell may hold an
+// accepted record of another session); otherwise upsert (key, value, block of the cell, column) and set bit cell & 63.
+// The cell comes from the local timestamp the session paths use (assign_ts).
+__global__ void __launch_bounds__(256) distinct_mark_session_kernel(DistMarkArgs a, const EngineConst* __restrict__ cp) {
+    const EngineConst& c = *cp;
+    unsigned int created = 0;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * blockDim.x) {
+        if (a.dmask[i]) continue;
+        const int64_t q = dist_cell(assign_ts(c, a.ts[i]), a.gap);
+        const uint64_t key = (uint64_t)a.keys[i];
+        const unsigned long long bit = 1ull << (q & 63);
+        for (int d = 0; d < a.nd; ++d) {
+            if (a.nul[d] && a.nul[d][i]) continue;
+            const uint64_t v = (uint64_t)a.src[d][i];
+            uint64_t slot = 0;
+            const int r = dist_upsert(a.tab, a.smask, key ? key : 1ull, v ? v : 1ull, dist_tag(q >> 6, key, v, d), &slot);
+            if (r < 0) { atomicAdd(a.ctr + 1, 1ull); continue; }
+            dist_or_bits(a.tab, slot, bit);
+            created += r > 0 ? 1u : 0u;
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) created += __shfl_down(created, o);    // the whole wave is back here
+    if ((threadIdx.x & 63) == 0 && created) atomicAdd(a.ctr + 2, (unsigned long long)created);
+}
+
 // The scans of the table give block b the slots [b * chunk, (b + 1) * chunk): the count pass leaves each block's live
 // count, from which the extract pass knows where the block's entries go without a shared cursor (one atomic on one
 // word per wave and iteration capped both passes at the rate of that word: ~50 ms for 2^28 slots).
@@ -274,6 +351,9 @@ __device__ __forceinline__ void dist_block_range(int64_t slots, int64_t* lo, int
 }
 
 // Entries of windows that have not fired: per block into bcnt[], and their sum with one atomic per block.
+// R: word 3 is a bitmap and an entry without bits is dead (session mode clears the bits of fired sessions; in range
+// mode every entry has a bit).
+template <bool R>
 __global__ void __launch_bounds__(256) distinct_count_kernel(const unsigned long long* tab, int64_t slots, int64_t q_min,
                                                             unsigned long long* ctr, unsigned int* bcnt) {
     __shared__ unsigned int tot;
@@ -284,7 +364,7 @@ __global__ void __launch_bounds__(256) distinct_count_kernel(const unsigned long
     unsigned int mine = 0;
     for (int64_t i = lo + threadIdx.x; i < hi; i += 256) {
         const unsigned long long t = tab[4 * i + 2];
-        mine += (t != 0ull && dist_tag_q(t) >= q_min) ? 1u : 0u;
+        mine += (t != 0ull && dist_tag_q(t) >= q_min && (!R || tab[4 * i + 3] != 0ull)) ? 1u : 0u;
     }
     for (int o = 32; o > 0; o >>= 1) mine += __shfl_down(mine, o);
     if ((threadIdx.x & 63) == 0 && mine) atomicAdd(&tot, mine);
@@ -321,11 +401,12 @@ __global__ void __launch_bounds__(256) distinct_rebuild_kernel(const unsigned lo
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < slots; i += (int64_t)gridDim.x * blockDim.x) {
         const ulonglong2 kv = *reinterpret_cast<const ulonglong2*>(tab + 4 * i);
         const unsigned long long t = tab[4 * i + 2];
-        if (t != 0ull && dist_tag_q(t) >= q_min) {
+        const unsigned long long bits = R ? tab[4 * i + 3] : 1ull;
+        if (t != 0ull && dist_tag_q(t) >= q_min && bits != 0ull) {
             uint64_t slot = 0;
             const int r = dist_upsert(ntab, nsmask, kv.x, kv.y, t, &slot);
             if (r < 0) atomicAdd(ctr + 1, 1ull);
-            else if (R) dist_or_bits(ntab, slot, tab[4 * i + 3]);
+            else if (R) dist_or_bits(ntab, slot, bits);
             made += r > 0 ? 1u : 0u;
         }
     }
@@ -361,7 +442,7 @@ __global__ void __launch_bounds__(256) distinct_extract_kernel(unsigned long lon
                 if (R) tab[4 * i + 3] = 0ull;
             }
         }
-        const bool livee = t != 0ull && dist_tag_q(t) >= q_min;
+        const bool livee = t != 0ull && dist_tag_q(t) >= q_min && (!R || bits != 0ull);
         const unsigned long long b = __ballot(livee);
         if (!b) continue;                                  // (wave-uniform)
         unsigned int off = 0;
@@ -420,6 +501,11 @@ struct DistRangeArgs {
     unsigned long long* r_sum[FWA_MAX_AGGS];   // ... per-row sum of the window's distinct values (plan-owned)
     unsigned long long* r_cnt[FWA_MAX_AGGS];   // ... and their number
     unsigned long long* ctr;
+    // session mode (rows by (key, block) in rtab, a multimap)
+    const int64_t* o_start;
+    int64_t* rblk;                             // the block slot h of rtab was entered under
+    int64_t gap;
+    unsigned long long* tabw;                  // the set, for the clear
 };
 
 __device__ __forceinline__ uint32_t dist_row_hash(int64_t key, int64_t end) {
@@ -508,6 +594,117 @@ __global__ void __launch_bounds__(256) dist_range_count_kernel(DistRangeArgs a) 
     if ((threadIdx.x & 63) == 0 && miss) atomicAdd(a.ctr + 3, (unsigned long long)miss);
 }
 
+// ---- session mode: the count of a firing step, and the clear behind it ----
+
+// The cell range of a fired session [start, end): its records lie in [start, end - gap].
+__device__ __forceinline__ void dist_sess_range(const DistRangeArgs& a, int64_t row, int64_t* c_lo, int64_t* c_hi) {
+    *c_lo = dist_cell(a.o_start[row], a.gap);
+    *c_hi = dist_cell(jm::wsub(a.o_end[row], a.gap), a.gap);
+    if (*c_hi < *c_lo) *c_hi = *c_lo;
+}
+
+// Sizing pre-pass, one thread per fired row: the 64-cell blocks the step's rows touch, summed into ctr[3] (one atomic
+// per wave). The row table is a multimap with one slot per (row, block), so its size cannot come from nrows alone.
+__global__ void __launch_bounds__(256) dist_sess_blocks_kernel(DistRangeArgs a) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    unsigned long long nb = 0;
+    if (i < a.nrows) {
+        int64_t c_lo, c_hi;
+        dist_sess_range(a, a.row0 + i, &c_lo, &c_hi);
+        nb = (unsigned long long)((c_hi >> 6) - (c_lo >> 6) + 1);
+    }
+    for (int o = 32; o > 0; o >>= 1) nb += __shfl_down(nb, o);
+    if ((threadIdx.x & 63) == 0 && nb) atomicAdd(a.ctr + 3, nb);
+}
+
+// Row index, one thread per fired row: its distinct columns and per-row sums start from 0, and the row enters the row
+// table once per block of its cell range under (key, block); the slot keeps the block, so a lookup of (key, B) meets a
+// row of many blocks once. Several fired sessions of one key may share a block: all of them stay in the chain.
+__global__ void __launch_bounds__(256) dist_sess_index_kernel(DistRangeArgs a) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.nrows) return;
+    const int64_t row = a.row0 + i;
+    for (int j = 0; j < a.na; ++j) a.o_agg[j][row] = 0ull;
+    for (int s = 0; s < a.ns; ++s) { a.r_sum[s][row] = 0ull; a.r_cnt[s][row] = 0ull; }   // (0: +0.0 as well)
+    int64_t c_lo, c_hi;
+    dist_sess_range(a, row, &c_lo, &c_hi);
+    const int64_t key = a.o_key[row];
+    for (int64_t B = c_lo >> 6; B <= (c_hi >> 6); ++B) {
+        uint32_t h = dist_row_hash(key, B) & a.rmask;
+        for (uint32_t probe = 0; probe <= a.rmask; ++probe, h = (h + 1) & a.rmask)
+            if (atomicCAS(a.rtab + h, 0u, (unsigned int)(i + 1)) == 0u) { a.rblk[h] = B; break; }
+    }
+}
+
+// The bits of entry (key, B) that lie in fired rows, visited one row at a time: f(row, mask of the row's range in B).
+// Slots are final here (the index kernel is an earlier launch), so the walk may stop at an empty one.
+template <typename F>
+__device__ __forceinline__ void dist_sess_rows_of(const DistRangeArgs& a, int64_t key, int64_t B, F f) {
+    uint32_t h = dist_row_hash(key, B) & a.rmask;
+    for (uint32_t probe = 0; probe <= a.rmask; ++probe, h = (h + 1) & a.rmask) {
+        const unsigned int r = a.rtab[h];
+        if (r == 0u) return;
+        if (a.rblk[h] != B) continue;
+        const int64_t row = a.row0 + (int64_t)r - 1;
+        if (a.o_key[row] != key) continue;
+        int64_t c_lo, c_hi;
+        dist_sess_range(a, row, &c_lo, &c_hi);
+        f(row, c_lo, c_hi, dist_block_mask(c_lo, c_hi, B));
+    }
+}
+
+// One thread per slot of the set. A live entry (key, value, B, d, bits) whose bits meet the cell range of a fired row
+// of (key, B) counts for that row iff no earlier block of the row's range holds the same (key, value, d) with bits in
+// the range (read-only probes, at most the session's block count). An entry that meets no row belongs to a session in
+// flight. S: as dist_range_count_kernel, the decoded value also goes to the row's sum and 1 to the row's count.
+template <bool S>
+__global__ void __launch_bounds__(256) dist_sess_count_kernel(DistRangeArgs a) {
+    int64_t lo, hi;
+    dist_block_range(a.slots, &lo, &hi);
+    for (int64_t i = lo + threadIdx.x; i < hi; i += 256) {
+        const ulonglong2 tb = *reinterpret_cast<const ulonglong2*>(a.tab + 4 * i + 2);
+        if (tb.x == 0ull || tb.y == 0ull) continue;
+        const ulonglong2 kv = *reinterpret_cast<const ulonglong2*>(a.tab + 4 * i);
+        const int64_t B = dist_tag_q(tb.x);
+        const int d = (int)(tb.x & 7ull);
+        dist_sess_rows_of(a, (tb.x & 8ull) ? 0 : (int64_t)kv.x, B,
+                          [&](int64_t row, int64_t c_lo, int64_t c_hi, unsigned long long m) {
+            if (!(tb.y & m)) return;
+            for (int64_t Bp = c_lo >> 6; Bp < B; ++Bp) {
+                const int64_t s = dist_find(a.tab, a.smask, kv.x, kv.y, (tb.x & 63ull) | ((uint64_t)Bp << 6));
+                if (s >= 0 && (a.tab[4 * s + 3] & dist_block_mask(c_lo, c_hi, Bp))) return;
+            }
+            for (int j = 0; j < a.na; ++j) if (a.agg_d[j] == d) atomicAdd(a.o_agg[j] + row, 1ull);
+            if (S) {
+                const unsigned long long v = (tb.x & 16ull) ? 0ull : kv.y;
+                for (int s = 0; s < a.ns; ++s) {
+                    if (a.sum_d[s] != d) continue;
+                    if (a.sum_f64[s]) atomicAdd(reinterpret_cast<double*>(a.r_sum[s] + row), __longlong_as_double((long long)v));
+                    else atomicAdd(a.r_sum[s] + row, v);
+                    atomicAdd(a.r_cnt[s] + row, 1ull);
+                }
+            }
+        });
+    }
+}
+
+// The clear, a launch behind the count (which reads other entries' bits): every entry drops the bits inside the cell
+// range of each fired row of its (key, block). One thread owns each slot and no marking pass runs beside it: plain
+// stores. An entry left without bits is dead; the next rebuild drops it.
+__global__ void __launch_bounds__(256) dist_sess_clear_kernel(DistRangeArgs a) {
+    int64_t lo, hi;
+    dist_block_range(a.slots, &lo, &hi);
+    for (int64_t i = lo + threadIdx.x; i < hi; i += 256) {
+        const ulonglong2 tb = *reinterpret_cast<const ulonglong2*>(a.tab + 4 * i + 2);
+        if (tb.x == 0ull || tb.y == 0ull) continue;
+        const unsigned long long k = a.tab[4 * i];
+        unsigned long long bits = tb.y;
+        dist_sess_rows_of(a, (tb.x & 8ull) ? 0 : (int64_t)k, dist_tag_q(tb.x),
+                          [&](int64_t, int64_t, int64_t, unsigned long long m) { bits &= ~m; });
+        if (bits != tb.y) a.tabw[4 * i + 3] = bits;
+    }
+}
+
 // ---- SUM / AVG(DISTINCT): the finish of the fired rows ----
 
 struct DistFinDesc {
@@ -589,13 +786,20 @@ int dist_plan(const fwa_config* u, DistinctPlan* P, fwa_config* icfg, std::strin
     if (hop && !(u->flags & FWA_CFG_DISTINCT_RANGE))
         return no("SLIDE / CUMULATE windows need FWA_CFG_DISTINCT_RANGE (a window of several slices needs the union of "
                   "their sets, which is not additive: the flag takes the count from the set at every fire)");
-    if (u->window_kind != FWA_TUMBLE && !hop)
+    const bool sess = u->window_kind == FWA_SESSION && (u->flags & FWA_CFG_DISTINCT_SESSION);
+    if (u->window_kind != FWA_TUMBLE && !hop && !sess)
         return no("only TUMBLE windows, and SLIDE / CUMULATE under FWA_CFG_DISTINCT_RANGE (a window of several slices "
-                  "needs the union of their sets, which is not additive)");
+                  "needs the union of their sets, which is not additive); a Table SESSION window of a fixed gap takes "
+                  "it under FWA_CFG_DISTINCT_SESSION");
     if (u->semantics != FWA_SEM_TABLE) return no("a Table aggregate (FWA_SEM_TABLE)");
     if (u->flags & FWA_CFG_REDUCE) return no("not a DataStream reduction");
     if (u->key_kind == FWA_KEY_PREHASHED)
         return no("PREHASHED keys are not supported (the set keeps no hash per entry to place it in a key group)");
+    if (sess && u->allowed_lateness_ms > 0)
+        return no("SESSION windows with allowed lateness are not supported (the cell bitmap is exact only when a "
+                  "session's fire and its cleanup coincide)");
+    if (sess && (u->flags & FWA_CFG_DYNAMIC_GAP))
+        return no("SESSION windows with a per-record gap are not supported (the cells need one fixed gap)");
     // the marked column of aggregate j's source column (created on first use), and what SUM / AVG(DISTINCT) adds to it
     auto column_of = [&](int j) {
         const fwa_agg_spec& s = u->aggs[j];
@@ -609,7 +813,15 @@ int dist_plan(const fwa_config* u, DistinctPlan* P, fwa_config* icfg, std::strin
         P->fd[j] = d;
         return d;
     };
-    if (hop) {
+    if (hop || sess) {
+        // session mode: the same rewrite, so the handle keeps every session route; the marking pass runs behind the
+        // ingest and needs its dropped-record indices on the device, which the internal configuration collects (the
+        // caller's own flags decide what fwa_late_records and fwa_get_config answer)
+        if (sess) {
+            P->sess = true;
+            P->gap = u->gap_ms;
+            icfg->flags |= FWA_CFG_LATE_INDICES;
+        }
         // range mode: a distinct aggregate -> COUNT(*), a BIGINT that is never NULL, shares column 0 and reads no value
         // column, so nothing is remapped and the handle keeps the two-phase ingest and the carried HOP sums; the fire
         // overwrites the column from the set (dist_range_count), sums go to plan-owned columns
@@ -694,7 +906,8 @@ int dist_plan(const fwa_config* u, DistinctPlan* P, fwa_config* icfg, std::strin
 void dist_free(DistinctPlan* P) {
     if (!P) return;
     for (void* p : {(void*)P->d_tab, (void*)P->d_mark, (void*)P->d_stage, (void*)P->d_ctr, (void*)P->d_side, (void*)P->d_bcnt,
-                    (void*)P->d_bpre, (void*)P->d_rtab, (void*)P->d_wins, (void*)P->d_rsum})
+                    (void*)P->d_bpre, (void*)P->d_rtab, (void*)P->d_wins, (void*)P->d_rsum, (void*)P->d_dmask,
+                    (void*)P->d_rblk})
         if (p) (void)hipFree(p);
     for (int j = 0; j < FWA_MAX_AGGS; ++j) {
         if (P->d_fout[j]) (void)hipFree(P->d_fout[j]);
@@ -709,7 +922,7 @@ void dist_free(DistinctPlan* P) {
 // First slice whose window has not fired at the handle's watermark (every lower slice drops its records), or
 // LONG_MIN_J when that is not known cheaply: skipping lower slices only keeps garbage out of the set.
 int64_t dist_qmin(const fwa_engine* e) {
-    if (e->wm == LONG_MIN_J) return LONG_MIN_J;
+    if (e->wm == LONG_MIN_J || (e->dist && e->dist->sess)) return LONG_MIN_J;   // (session mode: live = has bits)
     auto fired = [&](int64_t q) {
         int64_t thr;
         bool always;
@@ -775,7 +988,8 @@ int64_t dist_pow2(int64_t x) {
 int dist_count_live(fwa_engine* e, int64_t q_min, int grid, int64_t* livee) {
     DistinctPlan* P = e->dist;
     HIPCHK(e, hipMemsetAsync(P->d_ctr, 0, 8, e->stream));
-    distinct_count_kernel<<<grid, 256, 0, e->stream>>>(P->d_tab, P->slots, q_min, P->d_ctr, P->d_bcnt);
+    if (P->range) distinct_count_kernel<true><<<grid, 256, 0, e->stream>>>(P->d_tab, P->slots, q_min, P->d_ctr, P->d_bcnt);
+    else distinct_count_kernel<false><<<grid, 256, 0, e->stream>>>(P->d_tab, P->slots, q_min, P->d_ctr, P->d_bcnt);
     HIPCHK(e, hipGetLastError());
     return dist_read_counter(e, livee);
 }
@@ -960,6 +1174,13 @@ int dist_mark(fwa_engine* e, const int64_t** keys, const int64_t** ts, const voi
         a.mark[d] = P->range ? nullptr : P->d_mark + (size_t)d * (size_t)P->mark_cap;
         a.wsum[d] = P->range || P->sidx[d] < 0 ? nullptr : P->d_mark + (size_t)(P->nd + P->sidx[d]) * (size_t)P->mark_cap;
     }
+    if (P->sess) {   // the pass runs behind the ingest (dist_mark_session): the room is reserved, the columns are held
+        P->hold.keys = a.keys;
+        P->hold.ts = a.ts;
+        for (int d = 0; d < P->nd; ++d) { P->hold.src[d] = a.src[d]; P->hold.nul[d] = a.nul[d]; }
+        P->hold.n = n;
+    }
+    if (!P->sess) {
     HIPCHK(e, hipMemsetAsync(P->d_ctr + 2, 0, 8, e->stream));
     HIPCHK(e, hipEventRecord(P->ev[0], e->stream));
     if (P->range) distinct_mark_range_kernel<<<grid_for(n, 1 << 16), 256, 0, e->stream>>>(a, e->d_ec);
@@ -971,6 +1192,7 @@ int dist_mark(fwa_engine* e, const int64_t** keys, const int64_t** ts, const voi
     HIPCHK(e, hipMemcpyAsync(P->h_ctr + 2, P->d_ctr + 2, 8, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(e, hipEventRecord(P->ev[2], e->stream));
     P->last_add = n * P->nd;
+    }
     // the internal layout: a source column that only distinct aggregates read is not passed on (its index may now hold
     // its marked column, or a DECIMAL piece); NULL flags only where the internal configuration still declares them
     for (int d = 0; d < P->nd; ++d) {
@@ -984,6 +1206,95 @@ int dist_mark(fwa_engine* e, const int64_t** keys, const int64_t** ts, const voi
         if (a.wsum[d]) vals[P->wcol[d]] = a.wsum[d];
     }
     for (int c = 0; c < FWA_MAX_COLS; ++c) if (!((e->cfg.nullable_cols >> c) & 1)) nulls[c] = nullptr;
+    return FWA_OK;
+}
+
+// Session mode: the marking pass of the push the ingest just settled (ok) -- or nothing, with the reserved room given
+// back, when the ingest refused the push. The set's bound was checked by dist_mark ahead of the ingest; the created
+// count comes back here, inside the call (the pass reads the caller's columns, so the call waits for it).
+int dist_mark_session(fwa_engine* e, bool ok) {
+    DistinctPlan* P = e->dist;
+    const int64_t n = P->hold.n;
+    if (n <= 0) return FWA_OK;
+    P->hold.n = 0;
+    const int64_t add = n * P->nd;
+    if (!ok) { P->bound -= std::min(P->bound, add); return FWA_OK; }
+    if (!e->d_dropidx || e->dropidx_cap < n) return fail(e, FWA_E_STATE, "COUNT(DISTINCT): the push kept no dropped-record list");
+    if (n > P->dmask_cap) {
+        if (P->d_dmask) HIPCHK(e, hipFree(P->d_dmask));
+        P->d_dmask = nullptr;
+        P->dmask_cap = 0;
+        const int64_t cap = std::max<int64_t>(n, 1 << 16);
+        HIPCHK(e, hipMalloc(&P->d_dmask, (size_t)cap));
+        P->dmask_cap = cap;
+    }
+    DistMarkArgs a;
+    memset(&a, 0, sizeof(a));
+    a.keys = P->hold.keys;
+    a.ts = P->hold.ts;
+    a.nd = P->nd;
+    a.n = n;
+    a.tab = P->d_tab;
+    a.smask = (uint64_t)P->slots - 1;
+    a.ctr = P->d_ctr;
+    a.dmask = P->d_dmask;
+    a.gap = P->gap;
+    for (int d = 0; d < P->nd; ++d) { a.src[d] = P->hold.src[d]; a.nul[d] = P->hold.nul[d]; }
+    HIPCHK(e, hipMemsetAsync(P->d_ctr + 1, 0, 16, e->stream));
+    HIPCHK(e, hipMemsetAsync(P->d_dmask, 0, (size_t)n, e->stream));
+    HIPCHK(e, hipEventRecord(P->ev[0], e->stream));
+    dist_drop_mask_kernel<<<grid_for(n, 1 << 10), 256, 0, e->stream>>>(e->d_dropidx, &e->d_st->drop_n, n, P->d_dmask);
+    HIPCHK(e, hipGetLastError());
+    distinct_mark_session_kernel<<<grid_for(n, 1 << 16), 256, 0, e->stream>>>(a, e->d_ec);
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, hipEventRecord(P->ev[1], e->stream));
+    P->timing = true;
+    HIPCHK(e, hipMemcpyAsync(P->h_ctr + 1, P->d_ctr + 1, 16, hipMemcpyDeviceToHost, e->stream));
+    if (int rc = stream_sync(e)) return rc;
+    if (P->h_ctr[1]) return fail(e, FWA_E_STATE, "COUNT(DISTINCT) set overflowed its bound");
+    const int64_t made = (int64_t)P->h_ctr[2];
+    if (made >= 0 && made <= add) P->bound -= add - made;
+    dist_collect_timing(e);
+    return FWA_OK;
+}
+
+// What the fire-time passes of range and session mode share: the set, the step's rows, the output column of every
+// COUNT_DISTINCT aggregate and the plan-owned per-row sums (grown here) of every summed column.
+int dist_fire_args(fwa_engine* e, int64_t row0, int64_t nrows, DistRangeArgs* ap) {
+    DistinctPlan* P = e->dist;
+    DistRangeArgs& a = *ap;
+    if (P->ns && row0 + nrows > P->rs_cap) {
+        if (P->d_rsum) HIPCHK(e, hipFree(P->d_rsum));
+        P->d_rsum = nullptr;
+        P->rs_cap = 0;
+        const int64_t cap = std::max<int64_t>(row0 + nrows + nrows / 4, 1 << 12);
+        HIPCHK(e, hipMalloc(&P->d_rsum, 16 * (size_t)cap * (size_t)P->ns));
+        P->rs_cap = cap;
+    }
+    a.tab = P->d_tab;
+    a.slots = P->slots;
+    a.smask = (uint64_t)P->slots - 1;
+    a.o_key = e->o_key;
+    a.o_end = e->o_end;
+    a.row0 = row0;
+    a.nrows = nrows;
+    a.ctr = P->d_ctr;
+    for (int j = 0; j < P->ucfg.num_aggs; ++j) {
+        if (!((P->cmask >> j) & 1)) continue;
+        const int oj = e->dec ? e->dec->umap[j] : j;       // (a DECIMAL plan renumbers the internal aggregates)
+        if (oj < 0) return fail(e, FWA_E_STATE, "COUNT(DISTINCT) aggregate has no output column");
+        for (int d = 0; d < P->nd; ++d) if (P->src[d] == P->ucfg.aggs[j].col) a.agg_d[a.na] = d;
+        a.o_agg[a.na++] = (unsigned long long*)e->o_agg[oj];
+    }
+    for (int d = 0; d < P->nd; ++d) {
+        if (P->sidx[d] < 0) continue;
+        const int s = P->sidx[d];
+        a.sum_d[s] = d;
+        a.sum_f64[s] = P->sf64[d];
+        a.r_sum[s] = P->d_rsum + (size_t)s * (size_t)P->rs_cap;
+        a.r_cnt[s] = P->d_rsum + (size_t)(P->ns + s) * (size_t)P->rs_cap;
+    }
+    a.ns = P->ns;
     return FWA_OK;
 }
 
@@ -1006,14 +1317,6 @@ int dist_range_count(fwa_engine* e, const std::set<std::pair<int64_t, int64_t>>&
         HIPCHK(e, hipMalloc(&P->d_wins, sizeof(DistWin) * (size_t)cap));
         P->wins_cap = cap;
     }
-    if (P->ns && row0 + nrows > P->rs_cap) {
-        if (P->d_rsum) HIPCHK(e, hipFree(P->d_rsum));
-        P->d_rsum = nullptr;
-        P->rs_cap = 0;
-        const int64_t cap = std::max<int64_t>(row0 + nrows + nrows / 4, 1 << 12);
-        HIPCHK(e, hipMalloc(&P->d_rsum, 16 * (size_t)cap * (size_t)P->ns));
-        P->rs_cap = cap;
-    }
     const int64_t rcap = dist_pow2(2 * nrows);
     if (rcap > P->rtab_cap) {
         if (P->d_rtab) HIPCHK(e, hipFree(P->d_rtab));
@@ -1025,34 +1328,11 @@ int dist_range_count(fwa_engine* e, const std::set<std::pair<int64_t, int64_t>>&
     if (int rc = upload(e, P->d_wins, hw.data(), sizeof(DistWin) * hw.size())) return rc;
     DistRangeArgs a;
     memset(&a, 0, sizeof(a));
-    a.tab = P->d_tab;
-    a.slots = P->slots;
-    a.smask = (uint64_t)P->slots - 1;
     a.wins = P->d_wins;
     a.nw = (int32_t)hw.size();
-    a.o_key = e->o_key;
-    a.o_end = e->o_end;
-    a.row0 = row0;
-    a.nrows = nrows;
     a.rtab = P->d_rtab;
     a.rmask = (uint32_t)(rcap - 1);
-    a.ctr = P->d_ctr;
-    for (int j = 0; j < P->ucfg.num_aggs; ++j) {
-        if (!((P->cmask >> j) & 1)) continue;
-        const int oj = e->dec ? e->dec->umap[j] : j;       // (a DECIMAL plan renumbers the internal aggregates)
-        if (oj < 0) return fail(e, FWA_E_STATE, "COUNT(DISTINCT) aggregate has no output column");
-        for (int d = 0; d < P->nd; ++d) if (P->src[d] == P->ucfg.aggs[j].col) a.agg_d[a.na] = d;
-        a.o_agg[a.na++] = (unsigned long long*)e->o_agg[oj];
-    }
-    for (int d = 0; d < P->nd; ++d) {
-        if (P->sidx[d] < 0) continue;
-        const int s = P->sidx[d];
-        a.sum_d[s] = d;
-        a.sum_f64[s] = P->sf64[d];
-        a.r_sum[s] = P->d_rsum + (size_t)s * (size_t)P->rs_cap;
-        a.r_cnt[s] = P->d_rsum + (size_t)(P->ns + s) * (size_t)P->rs_cap;
-    }
-    a.ns = P->ns;
+    if (int rc = dist_fire_args(e, row0, nrows, &a)) return rc;
     HIPCHK(e, hipMemsetAsync(P->d_rtab, 0, sizeof(unsigned int) * (size_t)rcap, e->stream));
     HIPCHK(e, hipMemsetAsync(P->d_ctr + 3, 0, 8, e->stream));
     HIPCHK(e, hipEventRecord(P->rev[0], e->stream));
@@ -1068,6 +1348,69 @@ int dist_range_count(fwa_engine* e, const std::set<std::pair<int64_t, int64_t>>&
     HIPCHK(e, hipMemcpyAsync(P->h_ctr + 3, P->d_ctr + 3, 8, hipMemcpyDeviceToHost, e->stream));
     if (int rc = stream_sync(e)) return rc;
     if (P->h_ctr[3]) return fail(e, FWA_E_STATE, "COUNT(DISTINCT): a counted value's (key, window) has no fired row");
+    float ms0 = 0.f, ms1 = 0.f;
+    HIPCHK(e, hipEventElapsedTime(&ms0, P->rev[0], P->rev[1]));
+    HIPCHK(e, hipEventElapsedTime(&ms1, P->rev[1], P->rev[2]));
+    P->index_ms += ms0;
+    P->count_ms += ms1;
+    P->count_steps++;
+    e->fire_ms += ms0 + ms1;
+    return FWA_OK;
+}
+
+// Session mode: the distinct columns of the rows [0, nrows) that fire_sessions just emitted (o_start / o_end are local
+// times), then the clear of their bits. On the handle's stream behind the fire, before the rows are handed out and
+// before any later push; synchronises. A step that fired nothing launches nothing.
+int dist_session_count(fwa_engine* e, int64_t nrows) {
+    DistinctPlan* P = e->dist;
+    if (nrows <= 0) return FWA_OK;
+    if (nrows >= (int64_t)1 << 31) return fail(e, FWA_E_STATE, "COUNT(DISTINCT): too many rows in one firing step");
+    if (int rc = dist_counters(e)) return rc;
+    DistRangeArgs a;
+    memset(&a, 0, sizeof(a));
+    if (int rc = dist_fire_args(e, 0, nrows, &a)) return rc;
+    a.o_start = e->o_start;
+    a.gap = P->gap;
+    a.tabw = P->d_tab;
+    const unsigned rgrid = (unsigned)((nrows + 255) / 256);
+    // the multimap's size: the blocks the rows touch, summed on the device
+    HIPCHK(e, hipMemsetAsync(P->d_ctr + 3, 0, 8, e->stream));
+    HIPCHK(e, hipEventRecord(P->rev[0], e->stream));
+    dist_sess_blocks_kernel<<<rgrid, 256, 0, e->stream>>>(a);
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, hipMemcpyAsync(P->h_ctr + 3, P->d_ctr + 3, 8, hipMemcpyDeviceToHost, e->stream));
+    if (int rc = stream_sync(e)) return rc;
+    const int64_t nblk = (int64_t)P->h_ctr[3];
+    if (nblk < nrows || nblk >= (int64_t)1 << 30)
+        return fail(e, FWA_E_STATE, "COUNT(DISTINCT): the fired sessions span too many 64-cell blocks for one step");
+    const int64_t rcap = dist_pow2(2 * nblk);
+    if (rcap > P->rtab_cap) {
+        if (P->d_rtab) HIPCHK(e, hipFree(P->d_rtab));
+        if (P->d_rblk) HIPCHK(e, hipFree(P->d_rblk));
+        P->d_rtab = nullptr;
+        P->d_rblk = nullptr;
+        P->rtab_cap = 0;
+        HIPCHK(e, hipMalloc(&P->d_rtab, sizeof(unsigned int) * (size_t)rcap));
+        HIPCHK(e, hipMalloc(&P->d_rblk, sizeof(int64_t) * (size_t)rcap));
+        P->rtab_cap = rcap;
+    }
+    a.rtab = P->d_rtab;
+    a.rblk = P->d_rblk;
+    a.rmask = (uint32_t)(rcap - 1);
+    HIPCHK(e, hipMemsetAsync(P->d_rtab, 0, sizeof(unsigned int) * (size_t)rcap, e->stream));
+    dist_sess_index_kernel<<<rgrid, 256, 0, e->stream>>>(a);
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, hipEventRecord(P->rev[1], e->stream));
+    if (P->d_tab) {   // (no table: nothing but NULLs was ever pushed, every count stays 0)
+        const int grid = grid_for(P->slots, kDistScanGrid);
+        if (P->ns) dist_sess_count_kernel<true><<<grid, 256, 0, e->stream>>>(a);
+        else dist_sess_count_kernel<false><<<grid, 256, 0, e->stream>>>(a);
+        HIPCHK(e, hipGetLastError());
+        dist_sess_clear_kernel<<<grid, 256, 0, e->stream>>>(a);
+        HIPCHK(e, hipGetLastError());
+    }
+    HIPCHK(e, hipEventRecord(P->rev[2], e->stream));
+    if (int rc = stream_sync(e)) return rc;
     float ms0 = 0.f, ms1 = 0.f;
     HIPCHK(e, hipEventElapsedTime(&ms0, P->rev[0], P->rev[1]));
     HIPCHK(e, hipEventElapsedTime(&ms1, P->rev[1], P->rev[2]));
@@ -1189,7 +1532,8 @@ int dist_snapshot_section(fwa_engine* e, std::vector<int64_t>* sec, int64_t* m_o
         const uint64_t t = w[2 * m + i];
         body[d] = (t & 8) ? 0 : (int64_t)w[i];
         body[m + d] = (t & 16) ? 0 : (int64_t)w[m + i];
-        body[2 * m + d] = slice_start(e, P->range ? qs[i] : dist_tag_q(t));
+        body[2 * m + d] = P->sess ? (int64_t)((uint64_t)qs[i] * (uint64_t)P->gap)   // the cell's start, local time
+                                  : slice_start(e, P->range ? qs[i] : dist_tag_q(t));
         body[3 * m + d] = (int64_t)(t & 7);
     }
     *m_out = m;
@@ -1211,7 +1555,7 @@ int dist_restore_section(fwa_engine* e, const int64_t* sec, int64_t m) {
         const uint64_t key = (uint64_t)body[lo + i], val = (uint64_t)body[m + lo + i];
         const int64_t d = body[3 * m + lo + i];
         if (d < 0 || d >= P->nd) return fail(e, FWA_E_ARG, "corrupt COUNT(DISTINCT) entry");
-        const int64_t q = slice_q(e, body[2 * m + lo + i]);
+        const int64_t q = P->sess ? dist_cell(body[2 * m + lo + i], P->gap) : slice_q(e, body[2 * m + lo + i]);
         w[i] = key ? key : 1ull;
         w[n + i] = val ? val : 1ull;
         w[2 * n + i] = dist_tag(P->range ? q >> 6 : q, key, val, (int)d);

@@ -2446,7 +2446,7 @@ int validate(const fwa_config* c) {
             return FWA_E_ARG;
     }
     if (c->flags & ~(FWA_CFG_DYNAMIC_GAP | FWA_CFG_LATE_INDICES | FWA_CFG_RECORD_LISTS | FWA_CFG_REDUCE | FWA_CFG_BY_LAST |
-                     FWA_CFG_DISTINCT_RANGE))
+                     FWA_CFG_DISTINCT_RANGE | FWA_CFG_DISTINCT_SESSION))
         return FWA_E_ARG;
     {   // DataStream built-in reductions (include/flink_amd.h FWA_CFG_REDUCE)
         int nby = 0, nsel = 0, nfirst = 0, nred = 0, nother = 0;
@@ -4287,6 +4287,11 @@ static int emit_late_rows(fwa_engine* e) {
     return FWA_OK;   // the caller clears late_rows once the output is final
 }
 
+// FWA_CFG_LATE_INDICES as the caller configured it (a DISTINCT plan may set it in the internal configuration only).
+static bool late_indices_wanted(const fwa_engine* e) {
+    return ((e->dist ? e->dist->ucfg.flags : e->cfg.flags) & FWA_CFG_LATE_INDICES) != 0;
+}
+
 // FWA_CFG_LATE_INDICES: fetch the dropped-record indices of the push just settled (ascending).
 static int collect_late_indices(fwa_engine* e) {
     unsigned long long m = 0;
@@ -4526,6 +4531,10 @@ int fwa_push_nullable(fwa_engine* e, const int64_t* keys, const int64_t* ts, con
         val_cols = vals;
     }
     if (!rc) rc = push_body(e, keys, ts, val_cols, null_cols, key_hash, n, flags, late_dropped_out);
+    if (e->dist && e->dist->sess) {   // session mode marks behind the ingest, and only what it accepted (distinct.inc)
+        const int rcm = dist_mark_session(e, rc == FWA_OK);
+        if (!rc) rc = rcm;
+    }
     for (int c = 0; c < FWA_MAX_COLS; ++c) e->dev_override[c] = nullptr;
     dist_collect_timing(e);
     return rc;
@@ -4600,7 +4609,8 @@ static int push_body(fwa_engine* e, const int64_t* keys, const int64_t* ts, cons
                               : err == FWA_E_ARG ? "Dynamic session time gap must satisfy 0 < gap"
                                                    : "key table full: raise fwa_config.key_capacity");
         }
-        if (a.dropidx) { int rc2 = collect_late_indices(e); if (rc2) return rc2; }
+        // (a session-mode DISTINCT plan collects the list for its own marking pass: the host copy is the caller's flag)
+        if (a.dropidx && late_indices_wanted(e)) { int rc2 = collect_late_indices(e); if (rc2) return rc2; }
         if (e->d_khash) { int rc2 = khash_fill(e, a.keys, a.key_hash, n); if (rc2) return rc2; }
         e->records_in += n;
         e->late_dropped += dropped;
@@ -5192,10 +5202,15 @@ static int snapshot_sessions(fwa_engine* e, fwa_blob* out) {
         off[kg[i] + 1]++;
     }
     for (int g = 0; g < maxp; ++g) off[g + 1] += off[g];
-    const size_t words = kSnapHdr + (size_t)maxp + 1 + (size_t)n * ncols;
+    std::vector<int64_t> dsec;                         // COUNT(DISTINCT): the set's live entries behind the body
+    int64_t dm = 0;
+    if (e->dist) { if (int rc = dist_snapshot_section(e, &dsec, &dm)) return rc; }
+    const size_t words0 = kSnapHdr + (size_t)maxp + 1 + (size_t)n * ncols, words = words0 + dsec.size();
     int64_t* b = (int64_t*)malloc(words * 8);
     if (!b) return fail(e, FWA_E_OOM, "snapshot blob allocation failed");
     snap_header(e, b, n);
+    b[28] = dm;
+    if (!dsec.empty()) memcpy(b + words0, dsec.data(), 8 * dsec.size());
     memcpy(b + kSnapHdr, off.data(), 8 * ((size_t)maxp + 1));
     int64_t* body = b + kSnapHdr + maxp + 1;
     std::vector<int64_t> cur(off.begin(), off.end() - 1);
@@ -5244,6 +5259,10 @@ static int restore_sessions(fwa_engine* e, const void* const* blobs, int32_t n_b
         const int64_t* off = h + kSnapHdr;
         const int64_t lo = off[e->cfg.kg_start], hi = off[e->cfg.kg_end + 1];
         if (lo < 0 || hi < lo || hi > n) return fail(e, FWA_E_ARG, "corrupt key-group offsets");
+        if (e->dist) {   // the set's entries of this handle's key groups, folded back into block and bit
+            const int ncols = 4 + na + nh + (e->cfg.key_kind == FWA_KEY_PREHASHED ? 1 : 0);
+            if (int rcd = dist_restore_section(e, off + maxp + 1 + (size_t)n * ncols, h[28])) return rcd;
+        }
         const int64_t m = hi - lo;
         if (m == 0) continue;
         const int64_t* body = off + maxp + 1;
@@ -5745,6 +5764,9 @@ int fwa_advance_watermark(fwa_engine* e, int64_t wm, fwa_out* out) {
     if (wm > e->wm && e->kind == FWA_SESSION) {
         int rc = fire_sessions(e, wm, &nrows);
         if (rc) return rc;
+        // COUNT(DISTINCT) over sessions: the fired rows' distinct columns come from the set now, and their bits are
+        // cleared -- behind the fire, ahead of the next push's bits (distinct.inc)
+        if (e->dist && e->dist->sess) { rc = dist_session_count(e, nrows); if (rc) return rc; }
         e->wm = wm;
     } else if (wm > e->wm && e->sparse) {   // windows with prev < maxTimestamp <= wm (every live one is > prev)
         int rc = sp_fire(e, sp_due(e, wm), 0, true, &nrows);
@@ -5921,7 +5943,7 @@ int fwa_get_stats(fwa_engine* e, fwa_stats* s) {
 
 int fwa_late_records(fwa_engine* e, const int32_t** idx, int64_t* n) {
     if (!e || !idx || !n) return FWA_E_ARG;
-    if (!(e->cfg.flags & FWA_CFG_LATE_INDICES)) return fail(e, FWA_E_STATE, "configure FWA_CFG_LATE_INDICES");
+    if (!late_indices_wanted(e)) return fail(e, FWA_E_STATE, "configure FWA_CFG_LATE_INDICES");
     if (int rc0 = settle_pending(e)) return rc0;
     *idx = e->late_idx.empty() ? nullptr : e->late_idx.data();
     *n = (int64_t)e->late_idx.size();

@@ -465,12 +465,17 @@ class WindowAggregator:
         self._settled()
         _check(rc, self.h)
 
+    def get_config(self):
+        """fwa_get_config: the caller's configuration (a DISTINCT or DECIMAL plan's internal one never shows, e.g. the
+        late indices a FWA_CFG_DISTINCT_SESSION handle collects for its own marking pass)."""
+        c = A.Config()
+        _check(lib().fwa_get_config(self.h, C.byref(c)), self.h)
+        return c
+
     @property
     def record_lists(self):
         """True when the handle keeps TUMBLE window state as record lists (FWA_CFG_RECORD_LISTS, chosen or auto)."""
-        c = A.Config()
-        _check(lib().fwa_get_config(self.h, C.byref(c)), self.h)
-        return bool(c.flags & A.CFG_RECORD_LISTS)
+        return bool(self.get_config().flags & A.CFG_RECORD_LISTS)
 
     def stats(self):
         st = A.Stats()

@@ -132,8 +132,8 @@ enum fwa_agg_kind {
  * JAVA_LONG, BINROW_BIGINT and GROUP_PREFIXED, any offset, a shift time zone, nullable columns, FWA_CFG_LATE_INDICES,
  * FWA_CFG_RECORD_LISTS (forced or auto-selected). FWA_E_UNSUPPORTED (fwa_last_error names COUNT(DISTINCT); for a
  * refused fwa_create, fwa_last_error(NULL) on the calling thread):
- *   FWA_SLIDE, FWA_CUMULATE without FWA_CFG_DISTINCT_RANGE (below), FWA_SESSION -- a window of several slices needs the
- *     union of the per-slice sets, which is not additive;
+ *   FWA_SLIDE, FWA_CUMULATE without FWA_CFG_DISTINCT_RANGE (below), FWA_SESSION without FWA_CFG_DISTINCT_SESSION (the
+ *     flag's comment, below) -- a window of several slices needs the union of the per-slice sets, which is not additive;
  *   FWA_SEM_DATASTREAM, FWA_CFG_REDUCE, FWA_KEY_PREHASHED -- the engine snapshot needs each entry's key group and no
  *     hash is kept per set entry;
  *   fwa_drain_partials, fwa_push_partials, fwa_drain_route, fwa_fire_partials -- a distinct count is not mergeable
@@ -323,6 +323,26 @@ typedef struct fwa_config {
 #define FWA_CFG_DISTINCT_RANGE 0x20 /* Table HOP / CUMULATE: allow FWA_COUNT_DISTINCT; the count of a window is taken
                                      * from the set at the fire (a pass over the live entries per firing step). No
                                      * effect on a TUMBLE handle (the marked-column path runs as without the flag). */
+#define FWA_CFG_DISTINCT_SESSION 0x40 /* Table SESSION with a fixed gap: allow FWA_COUNT_DISTINCT and FWA_AGG_DISTINCT on
+                                       * FWA_SUM_I64 / SUM_F64 / AVG_I64 / AVG_F64, with the semantics they have on the
+                                       * other window kinds (64-bit equality, NULLs skipped, COUNT never NULL, SUM / AVG
+                                       * NULL without a non-NULL value); a shift time zone is supported. The set keeps
+                                       * one entry per (key, value, column, block of 64 cells), a cell being
+                                       * floor(local timestamp / gap_ms), with a bitmap of the cells the value occurred
+                                       * in. A pass behind each push's ingest sets the bits of the records the ingest
+                                       * accepted (FWA_PUSH_ASYNC settles inside the call); every watermark step that
+                                       * fires sessions counts their rows from the set and then clears their bits. Both
+                                       * passes are what the flag opts into (FWA_OPT_DISTINCT_INDEX_US / COUNT_US /
+                                       * COUNT_STEPS report the fire's share). Still FWA_E_UNSUPPORTED (naming DISTINCT):
+                                       * allowed_lateness_ms > 0, FWA_CFG_DYNAMIC_GAP, FWA_SEM_DATASTREAM,
+                                       * FWA_CFG_REDUCE, FWA_KEY_PREHASHED, the partial-accumulator and heap-layout
+                                       * entry points. fwa_late_records answers as the caller's own flags say, and
+                                       * fwa_get_config returns them. A push that the ingest refuses marks nothing; a
+                                       * failure of the marking pass itself, behind a successful ingest, leaves the
+                                       * handle to be destroyed and restored from its last snapshot. fwa_snapshot /
+                                       * fwa_restore carry the set: one section entry per set bit, its slice start the
+                                       * cell's start (cell * gap_ms, local time). No effect on a handle that is not
+                                       * SESSION; without it a SESSION handle refuses the distinct aggregates. */
 
 typedef struct fwa_out {
     int64_t n_rows;
@@ -631,10 +651,12 @@ enum fwa_option {
                                     combiner block's slice window and were applied after its last merge (fwa_get_option) */
     FWA_OPT_KEY_TABLE_DIGEST = 22,/* read only: FNV-1a digest of the key table's words in slot order (fwa_get_option;
                                      diagnostic: equal for two handles that placed every key in the same slot) */
-    FWA_OPT_DISTINCT_INDEX_US = 23, /* read only, FWA_CFG_DISTINCT_RANGE: device microseconds the firing steps so far spent
-                                       indexing their rows (also part of fwa_stats.fire_ms) */
-    FWA_OPT_DISTINCT_COUNT_US = 24, /* read only, FWA_CFG_DISTINCT_RANGE: ... and scanning the set for the counts */
-    FWA_OPT_DISTINCT_COUNT_STEPS = 25 /* read only, FWA_CFG_DISTINCT_RANGE: firing steps counted so far */
+    FWA_OPT_DISTINCT_INDEX_US = 23, /* read only, FWA_CFG_DISTINCT_RANGE or FWA_CFG_DISTINCT_SESSION handles: device
+                                       microseconds the firing steps so far spent indexing their rows (also part of
+                                       fwa_stats.fire_ms) */
+    FWA_OPT_DISTINCT_COUNT_US = 24, /* read only, the same handles: ... and scanning the set for the counts (session
+                                       mode: the clear of the fired sessions' bits included) */
+    FWA_OPT_DISTINCT_COUNT_STEPS = 25 /* read only, the same handles: firing steps counted so far */
 };
 int fwa_set_option(fwa_engine* e, int32_t option, int64_t value);
 /* The option's effective value: for the tri-state options 1 if the handle currently takes that path (forced, or
