@@ -18,9 +18,17 @@
 //             decodes the elements in parallel into SoA columns (key, ts, value columns, NULL flags) and an
 //             event list (watermark / status / latency marker / record attributes) with record positions.
 //
+// Rows with STRING fields (FWA_FIELD_STRING) make records of varying length: the kernels are instantiated a second
+// time (VAR) in which a record header is valid when its length is in range and equals the row's own size int, the
+// walk falls back to listed scalar steps when consecutive elements differ in size, and the decode pass writes, per
+// STRING field, the length, NULL flag and input byte offset of every record's value. fwa_wire_strings_of turns those
+// into Arrow-style offsets (device scan) and bytes (gather from the still-resident wire bytes) on demand. The
+// fixed-length instantiation is the code as it was.
+//
 // HBM traffic: the wire bytes are read twice (scan, decode), the maps are S x 4 B per 4 KiB chunk, the
 // columns are written once. Bound: HBM (wire decoder).
 #include <hip/hip_runtime.h>
+#include <hipcub/hipcub.hpp>
 
 #include <algorithm>
 #include <cstdio>
@@ -34,6 +42,8 @@ namespace {
 
 constexpr int kChunk = 4096;            // bytes per chunk
 constexpr int kMaxStep = 253;           // S limit: entry offsets < S must fit a byte next to two status codes
+constexpr uint32_t kMaxBody = kMaxStep - 4;   // longest element body (the length prefix's value)
+constexpr int kNone = 9;                // scan: no candidate at this lane (past S, or already settled)
 constexpr uint32_t kNxtEnd = 0xFE;      // chain ends inside the chunk (stream end or partial element)
 constexpr uint32_t kNxtCorrupt = 0xFF;  // chain hits a malformed element
 constexpr uint32_t kDead = 0xFF;        // resolve: chunk lies after the stream's END (nothing to decode)
@@ -50,6 +60,8 @@ struct WireConst {
     int32_t key_field, ts_field, num_cols;
     int32_t col_field[FWA_MAX_COLS];
     int32_t row_size, nullbits;        // ROWDATA: BinaryRowData size (fixed part only) and null-bit-set width
+    int32_t nstr;                      // STRING fields (> 0: records vary in length, the VAR kernels run)
+    int32_t str_field[FWA_WIRE_MAX_FIELDS];
 };
 
 struct WireStatus {
@@ -98,6 +110,13 @@ __device__ __forceinline__ void stage_chunk(uint32_t* words, const uint8_t* __re
 // The chain step shared by scan and decode: classify the element starting at p (rem = bytes left in the stream
 // from the chunk start). Returns 0: a whole element of length 4 + *len; 1: END; 2: CORRUPT. The expected body
 // lengths are selected from uniform values (no per-lane indexed load of the kernel argument).
+//
+// VAR (rows with STRING fields): body[0] / body[1] are the shortest record bodies (fixed part only). A record header
+// is accepted when its length is at least that, the row's size int equals the length minus the header (a 32-bit
+// equality, which keeps false candidates as rare as the exact length does for fixed rows), the element is within the
+// 249-byte ceiling (else 3: TOO LONG) and the RowKind byte is INSERT (else 4, *tag = 256 + RowKind). The order of
+// these checks is part of the format the tests' reference decoder restates.
+template <bool VAR>
 __device__ __forceinline__ int element_at(const Lds& b, int p, int rem, const WireConst& w, uint32_t* len,
                                           int* tag) {
     if (p + 5 > rem) return 1;
@@ -106,6 +125,20 @@ __device__ __forceinline__ int element_at(const Lds& b, int p, int rem, const Wi
     *tag = t;
     const int32_t want = t == 0 ? w.body[0] : t == 1 ? w.body[1] : t == 2 ? w.body[2] : t == 3 ? w.body[3]
                        : t == 4 ? w.body[4] : t == 5 ? w.body[5] : -1;
+    if constexpr (VAR) {
+        if (t <= 1) {
+            const int hdr = t == 0 ? 13 : 5;                       // tag, [timestamp], size int
+            if (l < (uint32_t)want) return 2;
+            if (p + 4 + hdr > rem) return 1;                       // the size int is not here yet
+            if (b.be32(p + hdr) != l - (uint32_t)hdr) return 2;
+            if (l > kMaxBody) return 3;
+            if (p + 4 + (int)l > rem) return 1;
+            const int kind = (int)b.byte(p + 4 + hdr);
+            if (kind != 0) { *tag = 256 + kind; return 4; }
+            *len = l;
+            return 0;
+        }
+    }
     if (l != (uint32_t)want) return 2;
     if (p + 4 + (int)l > rem) return 1;
     *len = l;
@@ -118,21 +151,26 @@ __device__ __forceinline__ int element_at(const Lds& b, int p, int rem, const Wi
 // lanes whose header is a whole element of size R is exactly the next stretch of the chain (each check confirms
 // the previous lane's boundary), one ballot per 64 elements. The first lane that fails is resolved by one scalar
 // step (another element kind / END / CORRUPT), which also sets the new R. visit(pos, tag, rec_before, evt_rank)
-// runs on the lane owning each element. Returns 0 (left the chunk: *stop >= kChunk), 1 END, 2 CORRUPT.
-template <class F>
+// runs on the lane owning each element. Returns 0 (left the chunk: *stop >= kChunk), 1 END, 2 CORRUPT (VAR: 3, 4).
+//
+// VAR: rows whose strings are all inline have one size and the speculation runs as above. When it misses twice in
+// a row (k = 0: sizes alternate), the wave lists up to 64 elements by uniform scalar steps, lane i keeping the i-th,
+// and the lanes visit them in parallel; it goes back to speculating after a list whose elements all had one size.
+template <bool VAR, class F>
 __device__ __forceinline__ int wave_walk(const Lds& b, int p, int remi, const WireConst& w, uint32_t* nrec,
                                          uint32_t* nevt, int* stop, int* badtag, F&& visit) {
     const int lane = threadIdx.x & 63;
     const uint64_t below = (1ull << lane) - 1;
     uint32_t nr = 0, ne = 0;
     int R = 0;
+    int miss = 0;
     for (;;) {
         if (p >= kChunk) { *nrec = nr; *nevt = ne; *stop = p; return 0; }
         if (R > 0) {
             const int pos = p + lane * R;
             uint32_t len = 0;
             int tag = 0;
-            const bool ok = pos < kChunk && element_at(b, pos, remi, w, &len, &tag) == 0 && (int)len + 4 == R;
+            const bool ok = pos < kChunk && element_at<VAR>(b, pos, remi, w, &len, &tag) == 0 && (int)len + 4 == R;
             const uint64_t m = __ballot(ok);
             const int k = ~m == 0 ? 64 : __builtin_ctzll(~m);
             const bool mine = lane < k;
@@ -142,10 +180,43 @@ __device__ __forceinline__ int wave_walk(const Lds& b, int p, int remi, const Wi
             ne += (uint32_t)__popcll(em);
             p += k * R;
             if (k == 64 || p >= kChunk) continue;
+            if constexpr (VAR) miss = k == 0 ? miss + 1 : 0;
+        }
+        if constexpr (VAR) {
+            if (miss >= 2) {
+                // The uniform steps read nothing but the length prefixes (every lane executes them, so they are kept
+                // to a load and an add); lane i then checks element i in full, and the longest prefix of valid elements
+                // is the chain: a length prefix is only followed after its own element proved valid.
+                int cnt = 0, mypos = p, q = p;
+                while (cnt < 64 && q < kChunk) {
+                    const uint32_t l = b.be32(q);                   // (stale bytes past the stream's end fail the check)
+                    if (lane == cnt) mypos = q;
+                    ++cnt;
+                    if (l > kMaxBody) break;                        // its lane settles it; nothing is listed behind it
+                    q += 4 + (int)l;
+                }
+                uint32_t len = 0;
+                int tag = 0;
+                const bool ok = lane < cnt && element_at<VAR>(b, mypos, remi, w, &len, &tag) == 0;
+                const uint64_t m = __ballot(ok);
+                const int k = ~m == 0 ? 64 : __builtin_ctzll(~m);   // <= cnt
+                const bool mine = lane < k;
+                const uint64_t rm = __ballot(mine && tag <= 1), em = __ballot(mine && tag > 1);
+                if (mine) visit(mypos, tag, nr + (uint32_t)__popcll(rm & below), ne + (uint32_t)__popcll(em & below));
+                nr += (uint32_t)__popcll(rm);
+                ne += (uint32_t)__popcll(em);
+                const int sz0 = __shfl((int)len, 0, 64);
+                const bool same = k >= 2 && __ballot(mine && (int)len != sz0) == 0;
+                if (k == cnt) p = q;                                // every listed element is valid: q is the next start
+                else p = __shfl(mypos, k, 64);                      // the first invalid one: the scalar step below names it
+                if (same) { R = 4 + sz0; miss = 0; }
+                else R = 0;
+                if (k == cnt) continue;
+            }
         }
         uint32_t len = 0;                                          // scalar step at p (uniform)
         int tag = 0;
-        const int st = element_at(b, p, remi, w, &len, &tag);
+        const int st = element_at<VAR>(b, p, remi, w, &len, &tag);
         if (st) { *nrec = nr; *nevt = ne; *stop = p; *badtag = tag; return st; }
         if (lane == 0) visit(p, tag, nr, ne);
         if (tag <= 1) ++nr; else ++ne;
@@ -202,32 +273,61 @@ __device__ __forceinline__ int stage_pf(uint32_t* buf, const uint8_t* __restrict
 
 // ---- scan: persistent 64-lane blocks, one chunk at a time. Candidates whose first header is already invalid
 // (nearly all of them on real data) are settled in one lane-parallel check; each surviving candidate is walked
-// by the whole wave. ----
+// by the whole wave.
+//
+// VAR: several candidates in [0, S) are starts of the same chain (one per element that begins there). The walk of the
+// first one leaves, at every element start below S, the records / events before it (vis[]); the map entries of those
+// later candidates are the walk's exit and its totals minus that rank, and they are not walked again. ----
+constexpr uint32_t kVisMark = 1u << 31, kVisDone = 1u << 30;
+template <bool VAR>
 __global__ __launch_bounds__(64) void wire_scan_kernel(const uint8_t* __restrict__ in, int64_t nbytes,
                                                         int64_t nchunks, WireConst w, bool aligned,
                                                         uint32_t* __restrict__ map0) {
     __shared__ uint32_t buf[kBufWords];
+    __shared__ uint32_t vis[VAR ? 256 : 1];
     const Lds b{buf};
     const int lane = threadIdx.x;
     Prefetch pf;
     if ((int64_t)blockIdx.x < nchunks) pf.issue(in, nbytes, blockIdx.x, (kChunk + w.step + 15) / 16, aligned);
     for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
+        if constexpr (VAR)
+            for (int i = lane; i < 256; i += 64) vis[i] = 0;      // (the barriers of stage_pf order this)
         const int remi = stage_pf(buf, in, nbytes, nchunks, c, c + gridDim.x, w, aligned, pf);
         for (int e0 = 0; e0 < w.step; e0 += 64) {
             const int e = e0 + lane;
             uint32_t len = 0;
             int tag = 0;
-            const int first = e < w.step ? element_at(b, e, remi, w, &len, &tag) : 3;
-            if (first == 1 || first == 2) map0[c * w.step + e] = first == 1 ? kNxtEnd : kNxtCorrupt;
+            int first = e < w.step ? element_at<VAR>(b, e, remi, w, &len, &tag) : kNone;
+            if constexpr (VAR)
+                if (first == 0 && (vis[e] & kVisDone)) first = kNone;  // settled by an earlier candidate's walk
+            if (first >= 1 && first < kNone) map0[c * w.step + e] = first == 1 ? kNxtEnd : kNxtCorrupt;
             uint64_t alive = __ballot(first == 0);
             while (alive) {
                 const int j = __builtin_ctzll(alive);
                 alive &= alive - 1;
                 uint32_t nrec = 0, nevt = 0;
                 int stop = 0, bt = 0;
-                const int r = wave_walk(b, e0 + j, remi, w, &nrec, &nevt, &stop, &bt, [](int, int, uint32_t, uint32_t) {});
-                const uint32_t nx = r == 0 ? (uint32_t)(stop - kChunk) : r == 1 ? kNxtEnd : kNxtCorrupt;
-                if (lane == 0) map0[c * w.step + e0 + j] = nx | (nrec << 8) | (nevt << 20);   // <= 683 elements per chunk
+                if constexpr (VAR) {
+                    const int S = w.step;
+                    const int r = wave_walk<VAR>(b, e0 + j, remi, w, &nrec, &nevt, &stop, &bt,
+                                                 [&](int pos, int, uint32_t rb, uint32_t eb) {
+                                                     if (pos < S) vis[pos] = kVisMark | rb | (eb << 12);
+                                                 });
+                    const uint32_t nx = r == 0 ? (uint32_t)(stop - kChunk) : r == 1 ? kNxtEnd : kNxtCorrupt;
+                    __syncthreads();
+                    for (int pos = lane; pos < S; pos += 64) {
+                        const uint32_t v = vis[pos];
+                        if (!(v & kVisMark)) continue;
+                        map0[c * S + pos] = nx | ((nrec - (v & 0xFFF)) << 8) | ((nevt - ((v >> 12) & 0xFFF)) << 20);
+                        vis[pos] = kVisDone;
+                    }
+                    __syncthreads();
+                    alive &= ~__ballot(e < S && (vis[e] & kVisDone));
+                } else {
+                    const int r = wave_walk<VAR>(b, e0 + j, remi, w, &nrec, &nevt, &stop, &bt, [](int, int, uint32_t, uint32_t) {});
+                    const uint32_t nx = r == 0 ? (uint32_t)(stop - kChunk) : r == 1 ? kNxtEnd : kNxtCorrupt;
+                    if (lane == 0) map0[c * w.step + e0 + j] = nx | (nrec << 8) | (nevt << 20);   // <= 683 elements per chunk
+                }
             }
         }
     }
@@ -327,7 +427,16 @@ struct DecodeOut {
     int64_t* evt_val;
     int64_t evt_cap;
     WireStatus* st;
+    // STRING field k of record g, at [k * str_stride + g]: value length, input byte offset of its first byte
+    // (an inline value points into its slot), NULL flag
+    int32_t* str_len;
+    int64_t* str_src;
+    uint8_t* str_null;
+    int64_t str_stride;
 };
+
+constexpr int kErrTooLong = 512;       // WireStatus.err_tag of an element over the ceiling (>= 256: RowKind + 256)
+constexpr int kErrSlot = 513;          // ... of a STRING slot pointing outside its row
 
 __device__ void raise_err(WireStatus* st, int code, int tag, int64_t pos) {
     if (atomicCAS(&st->error, 0, code) == 0) {
@@ -357,7 +466,9 @@ __device__ __forceinline__ bool field_null(const Lds& b, int row, int f) {   // 
 }
 
 // ---- decode: persistent 64-lane blocks; the chunk's true chain is walked from its resolved entry and every
-// element is decoded by the lane that confirmed it ----
+// element is decoded by the lane that confirmed it. VAR: element_at has already checked the row's size int and
+// RowKind; every STRING slot is checked against the row here, before anything reads the value's bytes ----
+template <bool VAR>
 __global__ __launch_bounds__(64) void wire_decode_kernel(const uint8_t* __restrict__ in, int64_t nbytes, int64_t nchunks,
                                                           WireConst w, bool aligned, const uint8_t* __restrict__ c_ent,
                                                           const uint64_t* __restrict__ c_rec,
@@ -379,7 +490,38 @@ __global__ __launch_bounds__(64) void wire_decode_kernel(const uint8_t* __restri
                 int64_t ts = (int64_t)0x8000000000000000LL;          // StreamRecord without timestamp
                 if (tag == FWA_TAG_REC_WITH_TIMESTAMP) { ts = (int64_t)b.be64(q); q += 8; }
                 bool knull = false;
-                if (w.format == FWA_WIRE_ROWDATA) {
+                if constexpr (VAR) {
+                    const int size = (int)b.be32(q);                 // == L - header, <= 249 (element_at)
+                    q += 4;
+                    if (w.ts_field >= 0 && field_null(b, q, w.ts_field)) { raise_err(o.st, FWA_E_ARG, tag, cs + p); return; }
+                    for (int j = 0; j < w.num_cols; ++j) o.col_null[j][g] = field_null(b, q, w.col_field[j]);
+                    if (w.key_field >= 0) {
+                        knull = field_null(b, q, w.key_field);
+                        o.key_null[g] = knull;
+                        o.key[g] = knull ? 0 : (int64_t)read_field(b, q, w.key_field, w);
+                    }
+                    for (int k = 0; k < w.nstr; ++k) {
+                        const int f = w.str_field[k];
+                        const uint64_t slot = b.le64(q + w.foff[f]);
+                        const bool isnull = field_null(b, q, f);
+                        int64_t src = cs + q + w.foff[f];
+                        uint32_t len = 0;
+                        if (!isnull) {
+                            if (slot >> 63) {                        // inline: length in the top byte, bytes below it
+                                len = (uint32_t)(slot >> 56) & 0x7f;
+                                if (len > 7) { raise_err(o.st, FWA_E_CORRUPT, kErrSlot, cs + p); len = 0; }
+                            } else {                                 // offset << 32 | length, inside the row
+                                const uint64_t off = slot >> 32, ln = slot & 0xffffffffull;
+                                if (off < (uint64_t)w.row_size || off + ln > (uint64_t)size) raise_err(o.st, FWA_E_CORRUPT, kErrSlot, cs + p);
+                                else { len = (uint32_t)ln; src = cs + q + (int64_t)off; }
+                            }
+                        }
+                        const int64_t at = k * o.str_stride + g;
+                        o.str_len[at] = (int32_t)len;
+                        o.str_src[at] = src;
+                        o.str_null[at] = isnull;
+                    }
+                } else if (w.format == FWA_WIRE_ROWDATA) {
                     if ((int32_t)b.be32(q) != w.row_size) { raise_err(o.st, FWA_E_UNSUPPORTED, tag, cs + p); return; }
                     q += 4;                                          // row bytes start; byte 0 = RowKind
                     if (b.byte(q) != 0) { raise_err(o.st, FWA_E_UNSUPPORTED, 256 + (int)b.byte(q), cs + p); return; }
@@ -388,8 +530,8 @@ __global__ __launch_bounds__(64) void wire_decode_kernel(const uint8_t* __restri
                     for (int j = 0; j < w.num_cols; ++j) o.col_null[j][g] = field_null(b, q, w.col_field[j]);
                     o.key_null[g] = knull;
                 }
-                o.key[g] = knull ? 0 : (int64_t)read_field(b, q, w.key_field, w);
-                o.ts[g] = w.ts_field >= 0 ? (int64_t)read_field(b, q, w.ts_field, w) : ts;
+                if constexpr (!VAR) o.key[g] = knull ? 0 : (int64_t)read_field(b, q, w.key_field, w);
+                o.ts[g] =w.ts_field >= 0 ? (int64_t)read_field(b, q, w.ts_field, w) : ts;
                 for (int j = 0; j < w.num_cols; ++j) {
                     const int f = w.col_field[j];
                     const uint64_t v = read_field(b, q, f, w);
@@ -415,12 +557,58 @@ __global__ __launch_bounds__(64) void wire_decode_kernel(const uint8_t* __restri
         };
         uint32_t nrec = 0, nevt = 0;
         int stop = 0, bt = 0;
-        const int r = wave_walk(b, (int)ent, remi, w, &nrec, &nevt, &stop, &bt, visit);
+        const int r = wave_walk<VAR>(b, (int)ent, remi, w, &nrec, &nevt, &stop, &bt, visit);
         if (threadIdx.x == 0) {
             if (r == 1) o.st->consumed = cs + stop;
             else if (r == 2) raise_err(o.st, FWA_E_CORRUPT, bt, cs + stop);
+            else if (r == 3) raise_err(o.st, FWA_E_UNSUPPORTED, kErrTooLong, cs + stop);
+            else if (r == 4) raise_err(o.st, FWA_E_UNSUPPORTED, bt, cs + stop);
         }
     }
+}
+
+// ---- string extraction (fwa_wire_strings_of): offsets = exclusive scan of the lengths (hipcub), then this gather.
+// Values average tens of bytes, so a wave takes 64 consecutive strings, whose output bytes are one contiguous
+// run, and copies that run byte-parallel: consecutive lanes write consecutive output bytes (coalesced) and find
+// their string by a binary search over the wave's 65 offsets in LDS; the reads stay within the few KiB of wire
+// bytes the 64 records came from. ----
+constexpr int kGatherWaves = 4;
+__global__ __launch_bounds__(64 * kGatherWaves) void wire_gather_kernel(const uint8_t* __restrict__ in,
+                                                                        const int64_t* __restrict__ src,
+                                                                        const int32_t* __restrict__ off, int64_t n,
+                                                                        uint8_t* __restrict__ out) {
+    __shared__ int32_t s_off[kGatherWaves][65];
+    __shared__ int64_t s_src[kGatherWaves][64];
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (int64_t bb = (int64_t)blockIdx.x * (64 * kGatherWaves); bb < n; bb += (int64_t)gridDim.x * (64 * kGatherWaves)) {
+        const int64_t base = bb + wv * 64;
+        const int m = (int)std::min<int64_t>(64, n - base);         // strings of this wave (<= 0: none)
+        __syncthreads();                                            // the previous round's reads are done
+        if (lane < m) { s_off[wv][lane] = off[base + lane]; s_src[wv][lane] = src[base + lane]; }
+        if (lane == 0 && m > 0) s_off[wv][m] = off[base + m];
+        __syncthreads();
+        if (m <= 0) continue;
+        const int32_t o0 = s_off[wv][0], total = s_off[wv][m] - o0;
+        for (int32_t j = lane; j < total; j += 64) {
+            const int32_t t = o0 + j;
+            int lo = 0, hi = m;                                     // last string with off <= t (skips empty ones)
+            while (hi - lo > 1) {
+                const int mid = (lo + hi) >> 1;
+                if (s_off[wv][mid] <= t) lo = mid; else hi = mid;
+            }
+            out[t] = in[s_src[wv][lo] + (t - s_off[wv][lo])];
+        }
+    }
+}
+
+// 64-bit total of the lengths (inputs of 2 GiB and more, where the int32 offsets could wrap)
+__global__ __launch_bounds__(256) void wire_len_sum_kernel(const int32_t* __restrict__ len, int64_t n,
+                                                            unsigned long long* __restrict__ total) {
+    unsigned long long s = 0;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        s += (unsigned long long)(uint32_t)len[i];
+    for (int d = 32; d > 0; d >>= 1) s += __shfl_down(s, d, 64);
+    if ((threadIdx.x & 63) == 0 && s) atomicAdd(total, s);
 }
 
 }  // namespace
@@ -455,6 +643,21 @@ struct fwa_wire_decoder {
     uint8_t* col_null[FWA_MAX_COLS] = {};
     uint8_t* key_null = nullptr;
     int64_t out_cap = 0;
+    // STRING fields: per-record pass outputs and the extraction's outputs, [nstr][out_cap + 1]
+    int32_t* str_len = nullptr;
+    int64_t* str_src = nullptr;
+    uint8_t* str_null = nullptr;
+    int32_t* str_off = nullptr;
+    uint8_t* str_bytes[FWA_WIRE_MAX_FIELDS] = {};
+    int64_t str_bytes_cap[FWA_WIRE_MAX_FIELDS] = {};
+    int64_t str_total[FWA_WIRE_MAX_FIELDS] = {};
+    bool str_done[FWA_WIRE_MAX_FIELDS] = {};      // extracted since the last decode
+    bool str_valid = false;                       // a decode succeeded and its input is taken to be resident
+    const uint8_t* last_in = nullptr;             // device bytes of the last decode (staging buffer or the caller's)
+    int64_t last_nbytes = 0, last_nrec = 0;
+    void* scan_tmp = nullptr;
+    size_t scan_tmp_cap = 0;
+    unsigned long long* d_total = nullptr;
     int64_t* d_evt_pos = nullptr;
     int32_t* d_evt_tag = nullptr;
     int64_t* d_evt_val = nullptr;
@@ -517,6 +720,18 @@ int grow_outputs(fwa_wire_decoder* d, int64_t n) {
         if (d->w.format == FWA_WIRE_ROWDATA && (rc = re((void**)&d->col_null[j], 1))) return rc;
     }
     if (d->w.format == FWA_WIRE_ROWDATA && (rc = re((void**)&d->key_null, 1))) return rc;
+    if (d->w.nstr > 0) {
+        const int64_t per = (int64_t)d->w.nstr * (cap + 1);
+        auto rs = [&](void** p, int64_t elem) -> int {
+            if (*p) WCK(hipFree(*p));
+            *p = nullptr;
+            WCK(hipMalloc(p, per * elem));
+            return 0;
+        };
+        if ((rc = rs((void**)&d->str_len, 4)) || (rc = rs((void**)&d->str_src, 8)) || (rc = rs((void**)&d->str_null, 1)) ||
+            (rc = rs((void**)&d->str_off, 4)))
+            return rc;
+    }
     d->out_cap = cap;
     return 0;
 }
@@ -558,19 +773,27 @@ int fwa_wire_create(const fwa_wire_schema* s, fwa_wire_decoder** out) {
     w.nullbits = ((s->arity + 63 + 8) / 64) * 8;                  // BinaryRowData.calculateBitSetWidthInBytes
     for (int f = 0; f < s->arity; ++f) {
         const int t = s->field[f];
-        if (t < FWA_FIELD_LONG || t > FWA_FIELD_INT) return bad(FWA_E_UNSUPPORTED, "unsupported field type");
+        if (t < FWA_FIELD_LONG || t > FWA_FIELD_STRING) return bad(FWA_E_UNSUPPORTED, "unsupported field type");
+        if (t == FWA_FIELD_STRING) {
+            if (s->format != FWA_WIRE_ROWDATA)
+                return bad(FWA_E_UNSUPPORTED, "STRING fields are decoded in ROWDATA rows only: a Tuple's StringSerializer writes "
+                                              "varint-prefixed UTF-16 code units, and DataStream String keys are PREHASHED");
+            w.str_field[w.nstr++] = f;
+        }
         w.ftype[f] = t;
         if (s->format == FWA_WIRE_TUPLE) { w.foff[f] = off; off += field_bytes(t); }
         else w.foff[f] = w.nullbits + 8 * f;
     }
     auto integral = [&](int f) { return f >= 0 && f < s->arity && (w.ftype[f] == FWA_FIELD_LONG || w.ftype[f] == FWA_FIELD_INT); };
-    if (!integral(s->key_field)) return bad(FWA_E_ARG, "key_field must be a LONG or INT field");
+    if (!(s->key_field == -1 && w.nstr > 0) && !integral(s->key_field))
+        return bad(FWA_E_ARG, "key_field must be a LONG or INT field (or -1 in a schema with STRING fields)");
     if (s->ts_field != -1 && !integral(s->ts_field)) return bad(FWA_E_ARG, "ts_field must be -1 or a LONG/INT field");
     w.key_field = s->key_field;
     w.ts_field = s->ts_field;
     w.num_cols = s->num_cols;
     for (int j = 0; j < s->num_cols; ++j) {
         if (s->col_field[j] < 0 || s->col_field[j] >= s->arity) return bad(FWA_E_ARG, "col_field out of range");
+        if (w.ftype[s->col_field[j]] == FWA_FIELD_STRING) return bad(FWA_E_ARG, "a STRING field cannot be a value column");
         w.col_field[j] = s->col_field[j];
     }
     int value_len;
@@ -586,10 +809,12 @@ int fwa_wire_create(const fwa_wire_schema* s, fwa_wire_decoder** out) {
     for (int t = 0; t < 6; ++t) mx = std::max(mx, w.body[t]);
     w.step = 4 + mx;
     if (w.step > kMaxStep) return bad(FWA_E_UNSUPPORTED, "elements longer than 249 bytes");
+    if (w.nstr > 0) w.step = kMaxStep;                            // records up to the ceiling; body[0..1] are the shortest
     d->device = s->device;
     hipError_t e;
     if ((e = hipSetDevice(d->device)) != hipSuccess || (e = hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking)) != hipSuccess ||
         (e = hipMalloc((void**)&d->d_st, sizeof(WireStatus))) != hipSuccess ||
+        (e = hipMalloc((void**)&d->d_total, 8)) != hipSuccess ||
         (e = hipHostMalloc((void**)&d->h_st, sizeof(WireStatus))) != hipSuccess ||
         (e = hipHostMalloc((void**)&d->h_root, 4 * sizeof(uint32_t))) != hipSuccess)
         return bad(FWA_E_DEVICE, hipGetErrorString(e));
@@ -611,12 +836,14 @@ void fwa_wire_destroy(fwa_wire_decoder* d) {
     if (d->device >= 0) (void)hipSetDevice(d->device);
     if (d->stream) (void)hipStreamSynchronize(d->stream);
     void* ps[] = {d->d_in, d->map0, d->lv_nxt, d->lv_nrec, d->lv_nevt, d->ent, d->rec, d->evt, d->key, d->ts,
-                  d->key_null, d->d_evt_pos, d->d_evt_tag, d->d_evt_val, d->d_st};
+                  d->key_null, d->d_evt_pos, d->d_evt_tag, d->d_evt_val, d->d_st, d->str_len, d->str_src, d->str_null,
+                  d->str_off, d->scan_tmp, d->d_total};
     for (void* p : ps) if (p) (void)hipFree(p);
     for (int j = 0; j < FWA_MAX_COLS; ++j) {
         if (d->col[j]) (void)hipFree(d->col[j]);
         if (d->col_null[j]) (void)hipFree(d->col_null[j]);
     }
+    for (auto p : d->str_bytes) if (p) (void)hipFree(p);
     if (d->h_st) (void)hipHostFree(d->h_st);
     if (d->h_root) (void)hipHostFree(d->h_root);
     for (auto& x : d->ev) if (x) (void)hipEventDestroy(x);
@@ -635,6 +862,7 @@ int fwa_wire_get_stats(fwa_wire_decoder* d, fwa_wire_stats* out) {
 int fwa_wire_decode(fwa_wire_decoder* d, const uint8_t* bytes, int64_t nbytes, int32_t flags, fwa_wire_batch* out) {
     if (!d || !out || nbytes < 0 || (nbytes > 0 && !bytes)) return fail(d, FWA_E_ARG, "bad arguments");
     memset(out, 0, sizeof(*out));
+    d->str_valid = false;
     WCK(hipSetDevice(d->device));
     const WireConst& w = d->w;
     const int S = w.step;
@@ -686,7 +914,9 @@ int fwa_wire_decode(fwa_wire_decoder* d, const uint8_t* bytes, int64_t nbytes, i
     WCK(hipMemsetAsync(d->d_st, 0, sizeof(WireStatus), st));
     WCK(hipEventRecord(d->ev[0], st));
     const unsigned grid = (unsigned)std::min<int64_t>(nchunks, kPersistBlocks);
-    hipLaunchKernelGGL(wire_scan_kernel, dim3(grid), dim3(64), 0, st, in, nbytes, nchunks, w, aligned, d->map0);
+    const bool var = w.nstr > 0;
+    if (var) hipLaunchKernelGGL(wire_scan_kernel<true>, dim3(grid), dim3(64), 0, st, in, nbytes, nchunks, w, aligned, d->map0);
+    else hipLaunchKernelGGL(wire_scan_kernel<false>, dim3(grid), dim3(64), 0, st, in, nbytes, nchunks, w, aligned, d->map0);
     WCK(hipGetLastError());
     WCK(hipEventRecord(d->ev[1], st));
     auto level_map = [&](int l) {
@@ -727,13 +957,19 @@ int fwa_wire_decode(fwa_wire_decoder* d, const uint8_t* bytes, int64_t nbytes, i
     for (int j = 0; j < FWA_MAX_COLS; ++j) { o.col[j] = d->col[j]; o.col_null[j] = d->col_null[j]; }
     o.key_null = d->key_null;
     o.st = d->d_st;
+    o.str_len = d->str_len;
+    o.str_src = d->str_src;
+    o.str_null = d->str_null;
+    o.str_stride = d->out_cap + 1;
     for (int pass = 0; pass < 2; ++pass) {
         o.evt_pos = d->d_evt_pos;
         o.evt_tag = d->d_evt_tag;
         o.evt_val = d->d_evt_val;
         o.evt_cap = d->evt_cap;
-        hipLaunchKernelGGL(wire_decode_kernel, dim3(grid), dim3(64), 0, st, in, nbytes, nchunks, w, aligned,
-                           d->ent, d->rec, d->evt, o);
+        if (var) hipLaunchKernelGGL(wire_decode_kernel<true>, dim3(grid), dim3(64), 0, st, in, nbytes, nchunks, w, aligned,
+                                    d->ent, d->rec, d->evt, o);
+        else hipLaunchKernelGGL(wire_decode_kernel<false>, dim3(grid), dim3(64), 0, st, in, nbytes, nchunks, w, aligned,
+                                d->ent, d->rec, d->evt, o);
         WCK(hipGetLastError());
         WCK(hipEventRecord(d->ev[2], st));
         WCK(hipMemcpyAsync(d->h_st, d->d_st, sizeof(WireStatus), hipMemcpyDeviceToHost, st));
@@ -756,8 +992,10 @@ int fwa_wire_decode(fwa_wire_decoder* d, const uint8_t* bytes, int64_t nbytes, i
         const WireStatus& hs = *d->h_st;
         if (hs.error) {
             char m[160];
-            if (hs.error == FWA_E_CORRUPT) snprintf(m, sizeof m, "Corrupt stream, found tag: %d (element at byte %lld)", hs.err_tag, (long long)hs.err_pos);
+            if (hs.error == FWA_E_CORRUPT && hs.err_tag < 256) snprintf(m, sizeof m, "Corrupt stream, found tag: %d (element at byte %lld)", hs.err_tag, (long long)hs.err_pos);
             else if (hs.error == FWA_E_ARG) snprintf(m, sizeof m, "NULL rowtime field in the row at byte %lld", (long long)hs.err_pos);
+            else if (hs.err_tag == kErrSlot) snprintf(m, sizeof m, "Corrupt stream: a STRING slot points outside its row (record at byte %lld)", (long long)hs.err_pos);
+            else if (hs.err_tag == kErrTooLong) snprintf(m, sizeof m, "element longer than the %d-byte limit at byte %lld", (int)kMaxBody, (long long)hs.err_pos);
             else if (hs.err_tag >= 256) snprintf(m, sizeof m, "RowKind %d at byte %lld: window aggregation consumes insert-only rows", hs.err_tag - 256, (long long)hs.err_pos);
             else snprintf(m, sizeof m, "row size differs from the schema's fixed-length row at byte %lld", (long long)hs.err_pos);
             return fail(d, hs.error, m);
@@ -774,16 +1012,78 @@ int fwa_wire_decode(fwa_wire_decoder* d, const uint8_t* bytes, int64_t nbytes, i
         out->n_records = nrec;
         out->n_events = nevt;
         out->consumed = hs.consumed;
-        out->key = d->key;
+        out->key = w.key_field >= 0 ? d->key : nullptr;
         out->ts = d->ts;
         for (int j = 0; j < w.num_cols; ++j) { out->col[j] = d->col[j]; out->col_null[j] = d->col_null[j]; }
-        out->key_null = d->key_null;
+        out->key_null = w.key_field >= 0 ? d->key_null : nullptr;
+        if (var) {
+            d->str_valid = true;
+            d->last_in = in;
+            d->last_nbytes = nbytes;
+            d->last_nrec = nrec;
+            for (auto& x : d->str_done) x = false;
+        }
         out->evt_pos = nevt ? d->h_evt_pos.data() : nullptr;
         out->evt_tag = nevt ? d->h_evt_tag.data() : nullptr;
         out->evt_val = nevt ? d->h_evt_val.data() : nullptr;
         return FWA_OK;
     }
     return fail(d, FWA_E_STATE, "event list did not settle");
+}
+
+int fwa_wire_strings_of(fwa_wire_decoder* d, int32_t field, fwa_wire_strings* out) {
+    if (!d || !out) return fail(d, FWA_E_ARG, "bad arguments");
+    memset(out, 0, sizeof(*out));
+    const WireConst& w = d->w;
+    int k = -1;
+    for (int i = 0; i < w.nstr; ++i) if (w.str_field[i] == field) k = i;
+    if (k < 0) return fail(d, FWA_E_ARG, "not a STRING field of the schema");
+    if (!d->str_valid) return fail(d, FWA_E_STATE, "no decoded batch: strings follow a successful fwa_wire_decode");
+    const int64_t n = d->last_nrec, stride = d->out_cap + 1;
+    const int32_t* len = d->str_len + k * stride;
+    int32_t* off = d->str_off + k * stride;
+    if (!d->str_done[k]) {
+        WCK(hipSetDevice(d->device));
+        hipStream_t st = d->stream;
+        if (d->last_nbytes >= (1ll << 31)) {                      // only then can the values reach 2^31 bytes
+            unsigned long long total = 0;
+            WCK(hipMemsetAsync(d->d_total, 0, 8, st));
+            hipLaunchKernelGGL(wire_len_sum_kernel, dim3(1024), dim3(256), 0, st, len, n, d->d_total);
+            WCK(hipGetLastError());
+            WCK(hipMemcpyAsync(&total, d->d_total, 8, hipMemcpyDeviceToHost, st));
+            WCK(hipStreamSynchronize(st));
+            if (total >= (1ull << 31)) return fail(d, FWA_E_UNSUPPORTED, "the field's values of one decode reach 2^31 bytes (int32 offsets)");
+        }
+        size_t tb = 0;                                            // n + 1 items: offsets[n] = the total (len[n] is not used)
+        WCK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, len, off, (int)(n + 1), st));
+        if (tb > d->scan_tmp_cap) {
+            if (d->scan_tmp) WCK(hipFree(d->scan_tmp));
+            d->scan_tmp = nullptr;
+            d->scan_tmp_cap = 0;
+            WCK(hipMalloc(&d->scan_tmp, tb));
+            d->scan_tmp_cap = tb;
+        }
+        WCK(hipcub::DeviceScan::ExclusiveSum(d->scan_tmp, tb, len, off, (int)(n + 1), st));
+        int32_t total = 0;
+        WCK(hipMemcpyAsync(&total, off + n, 4, hipMemcpyDeviceToHost, st));
+        WCK(hipStreamSynchronize(st));
+        int rc = grow(d, &d->str_bytes[k], &d->str_bytes_cap[k], std::max<int64_t>(total, 1));
+        if (rc) return rc;
+        if (total > 0) {
+            const unsigned grid = (unsigned)std::min<int64_t>((n + 64 * kGatherWaves - 1) / (64 * kGatherWaves), 256 * 16);
+            hipLaunchKernelGGL(wire_gather_kernel, dim3(grid), dim3(64 * kGatherWaves), 0, st, d->last_in, d->str_src + k * stride,
+                               off, n, d->str_bytes[k]);
+            WCK(hipGetLastError());
+            WCK(hipStreamSynchronize(st));
+        }
+        d->str_total[k] = total;
+        d->str_done[k] = true;
+    }
+    out->offsets = off;
+    out->bytes = d->str_bytes[k];
+    out->null = d->str_null + k * stride;
+    out->total_bytes = d->str_total[k];
+    return FWA_OK;
 }
 
 }  // extern "C"

@@ -10,6 +10,10 @@ It pushes each run of records between two events straight from HBM into the wind
 events in stream order: a watermark that advances the channel's watermark fires windows
 (processWatermark), WatermarkStatus IDLE / ACTIVE toggles the channel, latency markers and record attributes
 are forwarded. No CPU fallback: the HIP library must be present.
+
+STRING fields (CHAR / VARCHAR / STRING of ROWDATA rows) come back through `DecodedBatch.strings(f)` as Arrow-style
+(offsets, bytes, null) device views; `NetworkInput(schema, engine, keydict=kd, key_parts=[...])` turns them and the
+value columns into key dictionary ids per run of records, so a VARCHAR-keyed Table job runs from the channel's bytes.
 """
 import ctypes as C
 
@@ -20,7 +24,7 @@ from .engine import EngineError, _is_torch_cuda, dev_view, lib
 
 MAX_FIELDS = 16
 FORMATS = {"TUPLE": 0, "ROWDATA": 1}
-FIELDS = {"LONG": 0, "DOUBLE": 1, "FLOAT": 2, "INT": 3}
+FIELDS = {"LONG": 0, "DOUBLE": 1, "FLOAT": 2, "INT": 3, "STRING": 4}
 FIELD_DTYPE = {0: "i8", 1: "f8", 2: "f4", 3: "i8"}           # value-column dtype per field type
 TAG_REC_WITH_TIMESTAMP, TAG_REC_WITHOUT_TIMESTAMP, TAG_WATERMARK, TAG_LATENCY_MARKER, TAG_STREAM_STATUS, \
     TAG_RECORD_ATTRIBUTES = range(6)
@@ -40,14 +44,19 @@ class Batch(C.Structure):
                 ("key_null", C.c_void_p), ("evt_pos", C.c_void_p), ("evt_tag", C.c_void_p), ("evt_val", C.c_void_p)]
 
 
+class Strings(C.Structure):                 # fwa_wire_strings
+    _fields_ = [("offsets", C.c_void_p), ("bytes", C.c_void_p), ("null", C.c_void_p), ("total_bytes", C.c_int64)]
+
+
 class WireStats(C.Structure):
     _fields_ = [("calls", C.c_int64), ("bytes_in", C.c_int64), ("records_out", C.c_int64),
                 ("decode_ms", C.c_double), ("scan_ms", C.c_double)]
 
 
 def make_schema(fields, key_field, ts_field=-1, cols=(), fmt="TUPLE", device=0, max_bytes=0):
-    """fields: field type names in value order ("LONG", "DOUBLE", "FLOAT", "INT"); ts_field -1 = the
-    StreamRecord timestamp; cols: the fields that become value columns 0, 1, ..."""
+    """fields: field type names in value order ("LONG", "DOUBLE", "FLOAT", "INT", and "STRING" in ROWDATA rows);
+    key_field -1 (schemas with a STRING field) = the caller builds the key; ts_field -1 = the StreamRecord
+    timestamp; cols: the fields that become value columns 0, 1, ..."""
     s = Schema()
     s.format = FORMATS[fmt]
     s.arity = len(fields)
@@ -74,6 +83,8 @@ def _bind(L):
     L.fwa_wire_decode.restype = C.c_int
     L.fwa_wire_get_stats.argtypes = [C.c_void_p, C.POINTER(WireStats)]
     L.fwa_wire_get_stats.restype = C.c_int
+    L.fwa_wire_strings_of.argtypes = [C.c_void_p, C.c_int32, C.POINTER(Strings)]
+    L.fwa_wire_strings_of.restype = C.c_int
     L._wire_bound = True
     return L
 
@@ -81,16 +92,17 @@ def _bind(L):
 class DecodedBatch:
     """Columns of one decode (torch CUDA views into decoder-owned HBM, valid until its next decode)."""
 
-    def __init__(self, schema, b):
+    def __init__(self, schema, b, decoder=None):
         self.n_records, self.n_events, self.consumed = b.n_records, b.n_events, b.consumed
+        self._decoder = decoder
         n = self.n_records
-        self.key = dev_view(b.key, n, np.dtype("i8"))
+        self.key = dev_view(b.key, n, np.dtype("i8")) if b.key else None
         self.ts = dev_view(b.ts, n, np.dtype("i8"))
         self.cols = [dev_view(b.col[j], n, np.dtype(FIELD_DTYPE[schema.field[schema.col_field[j]]]))
                      for j in range(schema.num_cols)]
         rowdata = schema.format == FORMATS["ROWDATA"]
         self.col_null = [dev_view(b.col_null[j], n, np.dtype("u1")) for j in range(schema.num_cols)] if rowdata else None
-        self.key_null = dev_view(b.key_null, n, np.dtype("u1")) if rowdata else None
+        self.key_null = dev_view(b.key_null, n, np.dtype("u1")) if rowdata and b.key_null else None
         ne = self.n_events
         if ne:
             self.evt_pos = np.ctypeslib.as_array(C.cast(b.evt_pos, C.POINTER(C.c_int64)), (ne,)).copy()
@@ -101,6 +113,12 @@ class DecodedBatch:
             self.evt_tag = np.zeros(0, np.int32)
             self.evt_val = np.zeros((0, 4), np.int64)
 
+    def strings(self, f):
+        """(offsets int32 [n + 1], bytes uint8, null uint8 [n]) of STRING field f: views valid until the decoder's
+        next decode. (offsets[a:b + 1], bytes) is what KeyDictionary.encode takes for records [a, b). Device input
+        of the decode must still be alive and unchanged at the first call per field (the extraction is lazy)."""
+        return self._decoder.strings_of(f, self.n_records)
+
 
 class WireDecoder:
     """One decoder per input channel (single-threaded, like the channel's record deserializer)."""
@@ -109,6 +127,7 @@ class WireDecoder:
         self.schema = schema
         self.L = _bind(lib())
         self.h = C.c_void_p()
+        self._input = None                        # device input of the last decode (read again by strings_of)
         rc = self.L.fwa_wire_create(C.byref(schema), C.byref(self.h))
         if rc:
             raise EngineError(rc, "fwa_wire_create")
@@ -120,16 +139,24 @@ class WireDecoder:
             import torch
             torch.cuda.current_stream(data.device).synchronize()   # the bytes' producer ran on torch's stream
             ptr, n, flags = C.c_void_p(data.data_ptr()), data.numel(), WIRE_DEVICE_BYTES
-            keep = data
+            keep = self._input = data
         else:
             arr = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray)) else np.ascontiguousarray(data, np.uint8)
             ptr, n, flags = arr.ctypes.data_as(C.c_void_p), arr.size, 0
-            keep = arr
-        rc = self.L.fwa_wire_decode(self.h, ptr, n, flags, C.byref(b))
+            keep, self._input = arr, None
+        rc =self.L.fwa_wire_decode(self.h, ptr, n, flags, C.byref(b))
         del keep
         if rc:
             raise EngineError(rc, self.L.fwa_wire_last_error(self.h).decode())
-        return DecodedBatch(self.schema, b)
+        return DecodedBatch(self.schema, b, self)
+
+    def strings_of(self, f, n):
+        s = Strings()
+        rc = self.L.fwa_wire_strings_of(self.h, f, C.byref(s))
+        if rc:
+            raise EngineError(rc, self.L.fwa_wire_last_error(self.h).decode())
+        return (dev_view(s.offsets, n + 1, np.dtype("i4")), dev_view(s.bytes, max(1, s.total_bytes), np.dtype("u1")),
+                dev_view(s.null, n, np.dtype("u1")))
 
     def stats(self):
         s = WireStats()
@@ -155,9 +182,19 @@ class NetworkInput:
     buffer is carried over (SpanningWrapper). Returns the window rows fired by the watermarks in it.
     """
 
-    def __init__(self, schema, engine):
+    def __init__(self, schema, engine, keydict=None, key_parts=None):
+        """keydict (flink_amd.keydict.KeyDictionary) with key_parts, the key row's fields in the dictionary's order,
+        each ("str", field) -- a STRING field of the schema -- or ("col", j) -- value column j: every run of records
+        is pushed under the ids keydict.encode gives its key rows (NULL flags included; a NULL grouping key is a
+        key like any other there). Without keydict the schema's key_field is the key, as before."""
+        if (keydict is None) != (key_parts is None):
+            raise EngineError(-1, "keydict and key_parts go together")
         self.decoder = WireDecoder(schema)
         self.engine = engine
+        self.keydict = keydict
+        self.key_parts = None if key_parts is None else [(k, int(i)) for k, i in key_parts]
+        if self.key_parts is not None and any(k not in ("str", "col") for k, _ in self.key_parts):
+            raise EngineError(-1, "key_parts entries are ('str', field) or ('col', j)")
         self.carry = b""
         self.watermark = A.LONG_MIN                 # the channel's last forwarded watermark (valve)
         self.idle = False
@@ -169,6 +206,8 @@ class NetworkInput:
     def _push(self, batch, a, b):
         if b <= a:
             return
+        if getattr(self, "keydict", None) is not None:
+            return self._push_dict(batch, a, b)
         if batch.key_null is not None and bool(batch.key_null[a:b].any()):
             raise EngineError(-7, "NULL grouping key: pass the key hash with FWA_KEY_PREHASHED instead")
         nulls = None
@@ -176,6 +215,23 @@ class NetworkInput:
             nulls = [c[a:b] for c in batch.col_null]
         self.late_dropped += self.engine.push(batch.key[a:b], batch.ts[a:b], [c[a:b] for c in batch.cols],
                                               nulls=nulls if nulls and self.engine.cfg.nullable_cols else None)
+        self.records_in += b - a
+
+    def _push_dict(self, batch, a, b):
+        cols, nulls = [], []
+        for kind, i in self.key_parts:
+            if kind == "str":
+                offs, data, nul = batch.strings(i)
+                cols.append((offs[a:b + 1], data))               # offsets need not start at 0 (fwa_key_strings)
+                nulls.append(nul[a:b])
+            else:
+                cols.append(batch.cols[i][a:b])
+                nulls.append(batch.col_null[i][a:b] if batch.col_null is not None else None)
+        ids = self.keydict.encode(cols, nulls)
+        vn = None
+        if batch.col_null is not None and self.engine.cfg.nullable_cols:
+            vn = [c[a:b] for c in batch.col_null]
+        self.late_dropped += self.engine.push(ids, batch.ts[a:b], [c[a:b] for c in batch.cols], nulls=vn)
         self.records_in += b - a
 
     def feed(self, buffer):
