@@ -27,6 +27,8 @@
 //
 // HBM traffic: the wire bytes are read twice (scan, decode), the maps are S x 4 B per 4 KiB chunk, the
 // columns are written once. Bound: HBM (wire decoder).
+//
+// The sender side (fwa_wire_encode: fired rows written as channel bytes) is wire_encode.inc, included at the end.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -1087,3 +1089,5 @@ int fwa_wire_strings_of(fwa_wire_decoder* d, int32_t field, fwa_wire_strings* ou
 }
 
 }  // extern "C"
+
+#include "wire_encode.inc"

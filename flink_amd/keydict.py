@@ -184,6 +184,38 @@ class KeyDictionary:
                 out.append(t.cpu().numpy())
         return (out, [z.cpu().numpy().astype(bool) for z in nul]) if with_nulls else out
 
+    def decode_device(self, ids):
+        """decode without leaving the device: (cols, nulls) of torch CUDA tensors, a STRING column as an
+        (offsets int32 [n + 1], bytes uint8) pair in Arrow layout -- what WireEncoder.encode takes as keycols."""
+        import torch
+        di = _dev(ids, np.int64)
+        n = len(di)
+        cols, souts, ptrs = [], {}, []
+        for c, k in enumerate(self.types):
+            if k == STRING:
+                o = torch.empty(n + 1, dtype=torch.int32, device="cuda")
+                so = KeyStringsOut(o.data_ptr(), None, 0, 0)
+                souts[c] = so
+                cols.append(o)
+                ptrs.append(C.addressof(so))
+            else:
+                t = torch.empty(n, dtype={0: torch.int64, 1: torch.int32, 2: torch.float64}[k], device="cuda")
+                cols.append(t)
+                ptrs.append(t.data_ptr())
+        nul = [torch.empty(n, dtype=torch.uint8, device="cuda") for _ in self.types]
+        carr = (C.c_void_p * max(1, len(ptrs)))(*ptrs)
+        torch.cuda.synchronize()
+        self._check(lib().fwa_keydict_decode(self.h, di.data_ptr(), n, carr, _ptrs(nul)), "fwa_keydict_decode")
+        if souts:
+            data = {}
+            for c, so in souts.items():
+                data[c] = torch.empty(max(1, so.needed), dtype=torch.uint8, device="cuda")
+                so.bytes, so.capacity = data[c].data_ptr(), so.needed
+            torch.cuda.synchronize()
+            self._check(lib().fwa_keydict_decode(self.h, di.data_ptr(), n, carr, _ptrs(nul)), "fwa_keydict_decode")
+            cols = [(t, data[c]) if c in souts else t for c, t in enumerate(cols)]
+        return cols, nul
+
     def size(self):
         return int(lib().fwa_keydict_size(self.h))
 

@@ -14,13 +14,20 @@ are forwarded. No CPU fallback: the HIP library must be present.
 STRING fields (CHAR / VARCHAR / STRING of ROWDATA rows) come back through `DecodedBatch.strings(f)` as Arrow-style
 (offsets, bytes, null) device views; `NetworkInput(schema, engine, keydict=kd, key_parts=[...])` turns them and the
 value columns into key dictionary ids per run of records, so a VARCHAR-keyed Table job runs from the channel's bytes.
+
+The other direction: `WireEncoder` binds fwa_wire_encode -- the SoA columns of a watermark step (fwa_out, and the decoded
+key dictionary columns of a Table job) become the bytes RecordWriter would have produced, in HBM -- and `NetworkOutput`
+is the mirror of RecordWriterOutput (flink-streaming-java/.../runtime/io/RecordWriterOutput.java:131-135 and its
+emitWatermark / emitWatermarkStatus / emitLatencyMarker / emitRecordAttributes): emit(wm) fires the engine and returns
+"rows, then the watermark" as channel bytes.
 """
 import ctypes as C
 
 import numpy as np
 
 from . import _abi as A
-from .engine import EngineError, _is_torch_cuda, dev_view, lib
+from .engine import EngineError, _host_to_np, _is_torch_cuda, dev_view, lib
+from .keydict import FIELD as KEY_FIELD, KeyStrings
 
 MAX_FIELDS = 16
 FORMATS = {"TUPLE": 0, "ROWDATA": 1}
@@ -269,3 +276,225 @@ class NetworkInput:
 
     def close(self):
         self.decoder.close()
+
+
+# ---- the sender side: fwa_wire_encode ----
+SOURCES = {"KEY": 0, "KEYCOL": 1, "WIN_START": 2, "WIN_END": 3, "WIN_TIME": 4, "AGG": 5}
+RECORD_TS = {None: 0, "NONE": 0, "WIN_TIME": 1}
+WIRE_HOST_BYTES = 0x2
+MAX_KEYCOLS = 8
+
+
+class OutSchema(C.Structure):               # fwa_wire_out_schema
+    _fields_ = [("format", C.c_int32), ("arity", C.c_int32), ("field", C.c_int32 * MAX_FIELDS),
+                ("src", C.c_int32 * MAX_FIELDS), ("src_index", C.c_int32 * MAX_FIELDS),
+                ("src_kind", C.c_int32 * MAX_FIELDS), ("record_ts", C.c_int32), ("device", C.c_int32),
+                ("max_bytes", C.c_int64)]
+
+
+class KeyCols(C.Structure):                 # fwa_wire_keycols
+    _fields_ = [("n_cols", C.c_int32), ("pad", C.c_int32), ("col", C.c_void_p * MAX_KEYCOLS),
+                ("null", C.c_void_p * MAX_KEYCOLS), ("str", KeyStrings * MAX_KEYCOLS)]
+
+
+class Event(C.Structure):                   # fwa_wire_event
+    _fields_ = [("tag", C.c_int32), ("pad", C.c_int32), ("val", C.c_int64 * 4)]
+
+
+class WireBytes(C.Structure):               # fwa_wire_bytes
+    _fields_ = [("dev", C.c_void_p), ("host", C.c_void_p), ("nbytes", C.c_int64)]
+
+
+class EncStats(C.Structure):                # fwa_wire_enc_stats
+    _fields_ = [("calls", C.c_int64), ("rows_in", C.c_int64), ("bytes_out", C.c_int64), ("encode_ms", C.c_double),
+                ("scan_ms", C.c_double), ("size_ms", C.c_double)]
+
+
+def make_out_schema(fields, fmt="TUPLE", record_ts=None, device=0, max_bytes=0):
+    """fields, in the value's order: (wire type, source) pairs. The wire type is "LONG" / "DOUBLE" / "FLOAT" / "INT", or
+    "STRING" in ROWDATA rows; the source is "KEY", "WIN_START", "WIN_END", "WIN_TIME" (win_end - 1), ("AGG", j, kind) with
+    the aggregate's kind name as in flink_amd._abi.AGG_KINDS (it fixes the dtype of the result column), or
+    ("KEYCOL", k, type) with the key dictionary column's type ("BIGINT" / "INT" / "DOUBLE" / "STRING").
+    record_ts: None (TAG_REC_WITHOUT_TIMESTAMP, Table rows) or "WIN_TIME" (the DataStream record timestamp win_end - 1).
+    The pairing of sources and wire types is checked by fwa_wire_enc_create (WireEncoder)."""
+    fields = list(fields)
+    if not 1 <= len(fields) <= MAX_FIELDS:
+        raise ValueError("arity %d out of range (1..%d)" % (len(fields), MAX_FIELDS))
+    if fmt not in FORMATS:
+        raise ValueError("unknown wire format %r" % (fmt,))
+    if record_ts not in RECORD_TS:
+        raise ValueError("record_ts is None or 'WIN_TIME', not %r" % (record_ts,))
+    s = OutSchema()
+    s.format, s.arity = FORMATS[fmt], len(fields)
+    for i, fs in enumerate(fields):
+        if not isinstance(fs, (tuple, list)) or len(fs) != 2:
+            raise ValueError("field %d: a (wire type, source) pair is expected, not %r" % (i, fs))
+        t, src = fs
+        if t not in FIELDS:
+            raise ValueError("field %d: unknown wire type %r" % (i, t))
+        s.field[i] = FIELDS[t]
+        if isinstance(src, str):
+            if src not in SOURCES or src in ("AGG", "KEYCOL"):
+                raise ValueError("field %d: source %r (AGG and KEYCOL are (name, index, kind) triples)" % (i, src))
+            s.src[i] = SOURCES[src]
+            continue
+        if len(src) != 3 or src[0] not in ("AGG", "KEYCOL"):
+            raise ValueError("field %d: source %r is not ('AGG', j, kind) or ('KEYCOL', k, type)" % (i, src))
+        name, j, kind = src
+        table, limit = (A.AGG_KINDS, A.FWA_MAX_AGGS) if name == "AGG" else (KEY_FIELD, MAX_KEYCOLS)
+        if kind not in table:
+            raise ValueError("field %d: unknown %s %r" % (i, "aggregate kind" if name == "AGG" else "key field type", kind))
+        if not 0 <= int(j) < limit:
+            raise ValueError("field %d: %s index %d out of range (0..%d)" % (i, name, j, limit - 1))
+        s.src[i], s.src_index[i], s.src_kind[i] = SOURCES[name], int(j), table[kind]
+    s.record_ts, s.device, s.max_bytes = RECORD_TS[record_ts], device, max_bytes
+    return s
+
+
+def _bind_enc(L):
+    if getattr(L, "_wire_enc_bound", False):
+        return L
+    L.fwa_wire_enc_create.argtypes = [C.POINTER(OutSchema), C.POINTER(C.c_void_p)]
+    L.fwa_wire_enc_create.restype = C.c_int
+    L.fwa_wire_enc_destroy.argtypes = [C.c_void_p]
+    L.fwa_wire_enc_destroy.restype = None
+    L.fwa_wire_enc_last_error.argtypes = [C.c_void_p]
+    L.fwa_wire_enc_last_error.restype = C.c_char_p
+    L.fwa_wire_encode.argtypes = [C.c_void_p, C.POINTER(A.Out), C.POINTER(KeyCols), C.POINTER(Event), C.c_int32,
+                                  C.c_int32, C.POINTER(WireBytes)]
+    L.fwa_wire_encode.restype = C.c_int
+    L.fwa_wire_enc_get_stats.argtypes = [C.c_void_p, C.POINTER(EncStats)]
+    L.fwa_wire_enc_get_stats.restype = C.c_int
+    L._wire_enc_bound = True
+    return L
+
+
+def _key_cols(keycols):
+    """(cols, nulls) as KeyDictionary.decode_device returns them -> fwa_wire_keycols and the tensors it points into."""
+    cols, nulls = keycols
+    if len(cols) > MAX_KEYCOLS:
+        raise EngineError(-1, "at most %d key columns" % MAX_KEYCOLS)
+    kc = KeyCols()
+    kc.n_cols = len(cols)
+    for c, col in enumerate(cols):
+        parts = col if isinstance(col, tuple) else (col,)
+        z = None if nulls is None else nulls[c]
+        for t in parts + ((z,) if z is not None else ()):
+            if t is not None and not _is_torch_cuda(t):
+                raise EngineError(-1, "key columns are CUDA tensors (KeyDictionary.decode_device)")
+        if isinstance(col, tuple):
+            kc.str[c].offsets, kc.str[c].bytes = col[0].data_ptr(), col[1].data_ptr()
+        elif col is not None:
+            kc.col[c] = col.data_ptr()
+        if z is not None:
+            kc.null[c] = z.data_ptr()
+    return kc
+
+
+class WireEncoder:
+    """One encoder per output channel (single-threaded, like the RecordWriter's serializer)."""
+
+    def __init__(self, schema):
+        self.schema = schema
+        self.L = _bind_enc(lib())
+        self.h = C.c_void_p()
+        rc = self.L.fwa_wire_enc_create(C.byref(schema), C.byref(self.h))
+        if rc:
+            raise EngineError(rc, self.L.fwa_wire_enc_last_error(None).decode() or "fwa_wire_enc_create")
+
+    def encode(self, out, keycols=None, events=(), host=False):
+        """out: the rows (flink_amd._abi.Out, as WindowAggregator.advance_watermark_raw returns them: device or host
+        columns); keycols: (cols, nulls) of KeyDictionary.decode_device for the KEYCOL sources; events: (tag, vals) of
+        the non-record elements written behind the rows. Returns the channel bytes: a zero-copy torch uint8 CUDA view
+        valid until the next encode, or with host=True (FWA_WIRE_HOST_BYTES) a bytes object."""
+        evs = list(events)
+        earr = (Event * max(1, len(evs)))()
+        for i, (tag, vals) in enumerate(evs):
+            earr[i].tag = int(tag)
+            for j, v in enumerate(list(vals)[:4]):
+                earr[i].val[j] = int(v)
+        kc = None if keycols is None else _key_cols(keycols)
+        if out.on_device or kc is not None:
+            import torch
+            torch.cuda.synchronize()                               # the columns' producers ran on torch's streams
+        b = WireBytes()
+        rc = self.L.fwa_wire_encode(self.h, C.byref(out), None if kc is None else C.byref(kc), earr, len(evs),
+                                    WIRE_HOST_BYTES if host else 0, C.byref(b))
+        if rc:
+            raise EngineError(rc, self.L.fwa_wire_enc_last_error(self.h).decode())
+        if host:
+            return C.string_at(b.host, b.nbytes) if b.nbytes else b""
+        return dev_view(b.dev, b.nbytes, np.dtype("u1"))
+
+    def stats(self):
+        s = EncStats()
+        self.L.fwa_wire_enc_get_stats(self.h, C.byref(s))
+        return s
+
+    def close(self):
+        if self.h:
+            self.L.fwa_wire_enc_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class NetworkOutput:
+    """One output channel behind a window engine handle: the mirror of RecordWriterOutput.
+
+    emit(wm) is the operator's watermark step seen from the channel: the windows wm completes fire, their rows are
+    written as StreamRecords in emission order and the watermark follows them (AbstractStreamOperator.processWatermark
+    :610-615). With keydict (the handle runs on key dictionary ids) the fired ids are decoded to their key columns on the
+    device and the schema's KEYCOL sources read those. The other elements go out as elements of their own."""
+
+    def __init__(self, schema, engine, keydict=None, host=False):
+        uses = any(schema.src[i] == SOURCES["KEYCOL"] for i in range(schema.arity))
+        if uses and keydict is None:
+            raise EngineError(-1, "the schema has KEYCOL sources: pass the handle's key dictionary")
+        self.encoder = WireEncoder(schema)
+        self.engine = engine
+        self.keydict = keydict
+        self.host = host
+        self.rows_out = 0
+
+    def _no_rows(self):
+        out = A.Out()
+        out.on_device, out.num_aggs = 1, A.FWA_MAX_AGGS
+        kc = None if self.keydict is None else ([None] * len(self.keydict.types), None)
+        return out, kc
+
+    def emit(self, wm, events=()):
+        """Advance the engine's watermark to wm; returns the bytes of the fired rows, the watermark, then `events`."""
+        out = self.engine.advance_watermark_raw(wm)
+        n = out.n_rows
+        kc = None
+        if self.keydict is not None:
+            if n:
+                i8 = np.dtype("i8")
+                ids = dev_view(out.key, n, i8) if out.on_device else _host_to_np(out.key, n, i8)
+                kc = self.keydict.decode_device(ids)
+            else:
+                kc = self._no_rows()[1]
+        self.rows_out += n
+        return self.encoder.encode(out, kc, [(TAG_WATERMARK, (int(wm),))] + list(events), host=self.host)
+
+    def _event(self, tag, vals):
+        out, kc = self._no_rows()
+        return self.encoder.encode(out, kc, [(tag, vals)], host=self.host)
+
+    def emit_watermark_status(self, status):
+        """WatermarkStatus IDLE (-1) / ACTIVE (0)."""
+        return self._event(TAG_STREAM_STATUS, (int(status),))
+
+    def emit_latency_marker(self, marked_time, operator_id_lower, operator_id_upper, subtask_index):
+        return self._event(TAG_LATENCY_MARKER, (marked_time, operator_id_lower, operator_id_upper, subtask_index))
+
+    def emit_record_attributes(self, is_backlog):
+        return self._event(TAG_RECORD_ATTRIBUTES, (1 if is_backlog else 0,))
+
+    def close(self):
+        self.encoder.close()

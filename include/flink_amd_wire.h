@@ -1,5 +1,6 @@
 /*
- * flink_amd_wire.h -- on-GPU decoding of Flink's network wire format.
+ * flink_amd_wire.h -- on-GPU decoding of Flink's network wire format, and, in the second
+ * half of this header, its encoding (fwa_wire_encode: fired rows written as channel bytes).
  *
  * Upstream of the window operator, Flink's StreamTask input deserialises every StreamElement of a channel
  * from its network buffers on the task thread, one virtual call chain per record:
@@ -159,6 +160,133 @@ typedef struct fwa_wire_strings {
     int64_t total_bytes;
 } fwa_wire_strings;
 int fwa_wire_strings_of(fwa_wire_decoder* d, int32_t field, fwa_wire_strings* out);
+
+/* ---- wire encoder: fired rows written as channel bytes on the GPU ----
+ *
+ * Downstream of the window operator, Flink's task thread sends every fired row through one virtual call chain:
+ *   RecordWriterOutput.collect -> pushToRecordWriter  (flink-streaming-java/.../runtime/io/RecordWriterOutput.java:
+ *     131-135: the SerializationDelegate around the StreamRecord)
+ *   -> RecordWriter.emit / serializeRecord  (flink-runtime/.../io/network/api/writer/RecordWriter.java:104-157: four
+ *     bytes are skipped, the element is written, the 4-byte big-endian length is put in front; the bytes are then
+ *     copied into the target subpartition's buffers, an element spanning buffers freely)
+ *   -> StreamElementSerializer.serialize  (StreamElementSerializer.java:158-187: tag byte, [long timestamp], value;
+ *     watermark, status, latency marker and record attributes with the payloads listed at fwa_wire_batch.evt_val)
+ *   -> the value serializer: TupleSerializer (big-endian fields back to back), or RowDataSerializer ->
+ *     BinaryRowDataSerializer.serialize (BinaryRowDataSerializer.java:85-93: int size, then the row's bytes as
+ *     BinaryRowWriter laid them out, AbstractBinaryWriter.java:80-105,279-334: RowKind in byte 0, the null bit of
+ *     field i at bit i + 8, 8-byte little-endian slots, INT / FLOAT in the low half of a zeroed slot, setNullAt
+ *     zeroing the slot, a STRING of at most 7 bytes in its slot with 0x80 | length in the top byte, a longer one in
+ *     the variable-length part, zero-padded to 8 bytes, slot = offset << 32 | length).
+ * fwa_wire_encode replaces that loop for the rows of one watermark step: the SoA columns fwa_advance_watermark returns
+ * (fwa_out), and for a dictionary-keyed Table job the key columns fwa_keydict_decode returns, become the bytes
+ *   be32 L | tag | [be64 ts] | value          per row, in row order, followed by the non-record elements given
+ * in HBM, byte for byte what the chain above writes. A watermark step is "rows, then the watermark"
+ * (AbstractStreamOperator.processWatermark :610-615). Cutting the bytes into 32 KiB network buffers stays with the
+ * caller; elements span buffers freely. The GPU decoder above is a receiver of these bytes.
+ *
+ * Limits. arity 1..FWA_WIRE_MAX_FIELDS; KEYCOL index < FWA_KEYDICT_MAX_ARITY; STRING fields in ROWDATA rows only
+ * (FWA_E_ARG); a TUPLE value cannot carry NULLs (FWA_E_ARG at encode when a source has NULL flags); DECIMAL aggregates
+ * are FWA_E_UNSUPPORTED (the reference row carries a DecimalData, non-compact for the DECIMAL(38) sums: the follow-up,
+ * matching the decoder's own limit). The decoder's 249-byte element ceiling does not apply: element offsets are 64-bit,
+ * and a STRING value may be as long as its int32 Arrow offsets allow. */
+
+/* Where a field's value comes from. */
+enum fwa_wire_src {
+    FWA_SRC_KEY = 0,        /* fwa_out.key                                                    (int64) */
+    FWA_SRC_KEYCOL = 1,     /* column src_index of fwa_wire_keycols (the decoded key dictionary row) */
+    FWA_SRC_WIN_START = 2,  /* fwa_out.win_start, as the engine returns it                    (int64) */
+    FWA_SRC_WIN_END = 3,    /* fwa_out.win_end, as the engine returns it                      (int64) */
+    FWA_SRC_WIN_TIME = 4,   /* win_end - 1: the window_time / TimeWindow.maxTimestamp column  (int64) */
+    FWA_SRC_AGG = 5         /* fwa_out.agg[src_index], NULL where fwa_out.agg_null[src_index] says so */
+};
+enum fwa_wire_record_ts {
+    FWA_REC_TS_NONE = 0,    /* TAG_REC_WITHOUT_TIMESTAMP (Table rows) */
+    FWA_REC_TS_WIN_TIME = 1 /* TAG_REC_WITH_TIMESTAMP, win_end - 1 (WindowOperator.emitWindowContents :552-557) */
+};
+
+/* The rows' layout on the wire. The field order is the caller's: a Table window TVF row is key fields, aggregates,
+ * window_start, window_end (AbstractWindowAggProcessor.collect :230-233); a legacy GROUP BY SESSION row orders its
+ * window properties as the query does.
+ * Allowed source -> wire type pairs (anything else is FWA_E_ARG at create): an int64 column -> LONG, or INT (the low
+ * 32 bits, Java's narrowing cast); an int32 column -> INT, or LONG (sign-extended); double -> DOUBLE; float -> FLOAT;
+ * a key dictionary STRING column -> STRING. FWA_FIRST_64 / FWA_SEL_64 hold a field's raw bits and also go out as
+ * DOUBLE, FWA_FIRST_32 / FWA_SEL_32 also as FLOAT. */
+typedef struct fwa_wire_out_schema {
+    int32_t format;                          /* enum fwa_wire_format */
+    int32_t arity;                           /* fields per value, 1..FWA_WIRE_MAX_FIELDS */
+    int32_t field[FWA_WIRE_MAX_FIELDS];      /* enum fwa_wire_field: the wire type of each field */
+    int32_t src[FWA_WIRE_MAX_FIELDS];        /* enum fwa_wire_src */
+    int32_t src_index[FWA_WIRE_MAX_FIELDS];  /* FWA_SRC_AGG: aggregate j (0..FWA_MAX_AGGS-1); FWA_SRC_KEYCOL: column k
+                                                (0..FWA_KEYDICT_MAX_ARITY-1); ignored otherwise */
+    int32_t src_kind[FWA_WIRE_MAX_FIELDS];   /* the result dtype of a column is not visible in fwa_out, so the schema
+                                                names it. FWA_SRC_AGG: the aggregate's fwa_agg_spec.kind (FWA_AGG_DISTINCT
+                                                bit allowed), which fixes its result column: [i64], [i32], [f64] or
+                                                [f32] as listed at enum fwa_agg_kind. FWA_SRC_KEYCOL: the column's enum
+                                                fwa_key_field_type. Ignored otherwise */
+    int32_t record_ts;                       /* enum fwa_wire_record_ts */
+    int32_t device;                          /* HIP device ordinal */
+    int64_t max_bytes;                       /* sizing hint: largest output per call (0 = 64 MiB; grows) */
+} fwa_wire_out_schema;
+
+/* The decoded key dictionary rows of the fired ids (fwa_keydict_decode on fwa_out.key), row i beside row i of the
+ * fwa_out. Always DEVICE pointers, also when the rows are host memory. */
+typedef struct fwa_wire_keycols {
+    int32_t n_cols;                                  /* columns given, <= FWA_KEYDICT_MAX_ARITY */
+    int32_t pad;
+    const void* col[FWA_KEYDICT_MAX_ARITY];          /* BIGINT int64 / INT int32 / DOUBLE double [n_rows]; unused for STRING */
+    const uint8_t* null[FWA_KEYDICT_MAX_ARITY];      /* [n_rows], 1 = NULL; NULL pointer = no NULLs in the column */
+    fwa_key_strings str[FWA_KEYDICT_MAX_ARITY];      /* STRING column: offsets [n_rows + 1] (need not start at 0), bytes;
+                                                        a NULL value's bytes are not read */
+} fwa_wire_keycols;
+
+/* A non-record element: tag 2..5 and the payload of fwa_wire_batch.evt_val. */
+typedef struct fwa_wire_event {
+    int32_t tag;                             /* enum fwa_wire_tag, FWA_TAG_WATERMARK..FWA_TAG_RECORD_ATTRIBUTES */
+    int32_t pad;
+    int64_t val[4];
+} fwa_wire_event;
+
+typedef struct fwa_wire_bytes {
+    const uint8_t* dev;                      /* device [nbytes], encoder-owned, valid until the next call on it */
+    const uint8_t* host;                     /* with FWA_WIRE_HOST_BYTES: a host copy (pinned, encoder-owned, valid as
+                                                long); NULL otherwise */
+    int64_t nbytes;
+} fwa_wire_bytes;
+
+/* fwa_wire_encode flag: also copy the bytes to host memory (a shim handing them to JVM network buffers). */
+#define FWA_WIRE_HOST_BYTES 0x2
+
+typedef struct fwa_wire_encoder fwa_wire_encoder;
+
+/* FWA_E_ARG: unknown format / field / source, arity or an index out of range, STRING in a TUPLE value, a source ->
+ * wire type pair that is not allowed. FWA_E_UNSUPPORTED: a DECIMAL aggregate source. FWA_E_DEVICE / FWA_E_OOM: HIP.
+ * fwa_wire_enc_last_error(NULL) says why a create failed (per thread). */
+int fwa_wire_enc_create(const fwa_wire_out_schema* schema, fwa_wire_encoder** out);
+void fwa_wire_enc_destroy(fwa_wire_encoder* e);
+const char* fwa_wire_enc_last_error(const fwa_wire_encoder* e);
+
+/* Row i of `rows` becomes element i; the n_events non-record elements follow the rows, in order (zero rows with events
+ * is legal, and so is neither: 0 bytes). rows->on_device == 0: the columns the schema reads are staged through the
+ * encoder, as the decoder stages host bytes. Device columns must be complete when the call is made (the encoder runs
+ * on its own stream); everything, the host copy included, is complete on return. keycols may be NULL when no field is
+ * FWA_SRC_KEYCOL.
+ * FWA_E_ARG: a column the schema reads is missing (KEYCOL without keycols / past n_cols, an aggregate past
+ * rows->num_aggs, a NULL pointer with n_rows > 0), an event tag outside 2..5, or a TUPLE schema whose source has NULL
+ * flags (a non-NULL agg_null / keycols->null pointer: TupleSerializer cannot write null fields).
+ * Device timing accumulates in fwa_wire_enc_stats. */
+int fwa_wire_encode(fwa_wire_encoder* e, const fwa_out* rows, const fwa_wire_keycols* keycols,
+                    const fwa_wire_event* events, int32_t n_events, int32_t flags, fwa_wire_bytes* out);
+
+typedef struct fwa_wire_enc_stats {
+    int64_t calls;
+    int64_t rows_in;
+    int64_t bytes_out;
+    double encode_ms;                        /* HIP-event device time of the encode kernels (size + scan + write) */
+    double scan_ms;                          /* of which: the exclusive scan to element offsets (STRING schemas) */
+    double size_ms;                          /* of which: the size pass (STRING schemas) */
+} fwa_wire_enc_stats;
+
+int fwa_wire_enc_get_stats(fwa_wire_encoder* e, fwa_wire_enc_stats* out);
 
 #ifdef __cplusplus
 }
