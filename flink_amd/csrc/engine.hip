@@ -327,12 +327,19 @@ __global__ void __launch_bounds__(kBlock) fire_kernel(FireArgs f, const EngineCo
 // retire only when every row fits out_cap (no count-and-relaunch). check_st: the fire was enqueued behind a push whose
 // status the host has not seen; spill_n / late_fire / error are final in stream order, and when one is set the host
 // discards this fire and fires again after the replay -- the kernel then emits and clears nothing.
+// retire == 2 (stale retirement): the touched flag is cleared but no identity is stored; the host
+// marks the slot stale and the next two-phase push that reaches it overwrites it (CombineArgs, ingest.inc).
+// gate: a speculative fire may list a slice whose slot was stale ahead of the pending push. 1: the slot holds the
+// slice's values only if that push reached the slice, qord inside the DevStatus min_q .. max_q of its Phase P (what its
+// combiner cleaned); outside, the window emits nothing. 2: the pending push does not know the slot: nothing either.
 // The window table travels in the kernel arguments: no upload.
 constexpr int kWalkMaxWin = 8;
 struct WalkWin {
     int64_t start, end;
     unsigned long long* base;   // the window's slot
     int32_t slot, retire;
+    int32_t gate, pad;
+    unsigned long long qord;    // jm::ord_i64 of the window's slice number (gate 1)
 };
 struct WalkArgs {
     const unsigned long long* key_table;
@@ -346,6 +353,7 @@ struct WalkArgs {
     DevStatus* st;
     int32_t* touched;
     int32_t nwin, check_st;
+    int32_t gated, pad;         // some window has a gate
     WalkWin win[kWalkMaxWin];
 };
 
@@ -382,6 +390,16 @@ __global__ void __launch_bounds__(kBlock) fire_walk_kernel(WalkArgs f, const Eng
     const uint32_t remk = (uint32_t)max((int64_t)0, min(nk - k0, (int64_t)kBlock * S));
     const uint32_t capr = (uint32_t)max((int64_t)0, min(f.capacity - k0, (int64_t)1 << 30));
     if (blockIdx.x == 0 && tid < f.nwin && f.win[tid].retire) f.touched[f.win[tid].slot] = 0;
+    // the gated windows that emit nothing, decided here: a read of the status inside the window loop would wait for
+    // the next window's loads, which are in flight ahead of it (r15: 0.42 ms per C2 fire instead of 0.17)
+    uint32_t shut_mask = 0;
+    if (f.gated) {
+        const unsigned long long q_lo = f.st->min_q, q_hi = f.st->max_q;
+        for (int w = 0; w < f.nwin; ++w) {
+            const int gate = f.win[w].gate;
+            if (gate != 0 && (gate != 1 || f.win[w].qord < q_lo || f.win[w].qord > q_hi)) shut_mask |= 1u << w;
+        }
+    }
     ulonglong2 kv[V];
     uint32_t pres = 0;                             // bit 2v + h: kid h of pair v holds a key
 #pragma unroll
@@ -400,7 +418,7 @@ __global__ void __launch_bounds__(kBlock) fire_walk_kernel(WalkArgs f, const Eng
     for (int w = 0; w < f.nwin; ++w) {
         const WalkWin win = f.win[w];
         if (w + 1 < f.nwin) walk_load<NA, V>(nxt, f.win[w + 1].base, f.stride, k0, rem, tid);
-        if (win.retire) {
+        if (win.retire == 1) {
 #pragma unroll
             for (int a = 0; a < NA; ++a) {
                 const unsigned long long id = (a > 0 && c.acc_kind[a] == ACC_MIN_ORD) ? ~0ull : 0ull;
@@ -414,10 +432,11 @@ __global__ void __launch_bounds__(kBlock) fire_walk_kernel(WalkArgs f, const Eng
         }
         uint32_t* wo = woff[w & 1];
         unsigned long long masks[S];
+        const bool shut = (shut_mask >> w) & 1u;
 #pragma unroll
         for (int s = 0; s < S; ++s) {
             const unsigned long long cnt = (s & 1) ? cur[0][s >> 1].y : cur[0][s >> 1].x;
-            masks[s] = __ballot(((pres >> s) & 1u) && cnt != 0);
+            masks[s] = __ballot(((pres >> s) & 1u) && cnt != 0 && !shut);
             if (lane == 0) wo[s * kWaves + wid] = (uint32_t)__popcll(masks[s]);
         }
         __syncthreads();
@@ -2187,6 +2206,13 @@ struct fwa_engine {
     int32_t reset_cap = 0;
     std::vector<int32_t> touched;     // host mirror
     std::vector<uint8_t> slot_clean;  // 1: a fire already restored the slot's identities (fire_slide)
+    // stale retirement: 1: the tumbling fire retired the slot without storing identities; its
+    // columns hold the fired window's values until a two-phase push overwrites them or clean_stale restores them
+    std::vector<uint8_t> stale;
+    int32_t n_stale = 0;
+    std::vector<std::pair<int64_t, int32_t>> push_stale;   // (slice, slot): stale slots the pending push may overwrite
+    int64_t stale_retires = 0;          // slots retired stale (FWA_OPT_STALE_RETIRES)
+    bool steady = false;                // the last settled push ran the two-phase ingest and needed no replay
     // slice directory
     DirEntry* d_dir = nullptr;
     bool dir_dirty = false;         // the host directory changed since the last publish (published before v1 ingest)
@@ -2589,6 +2615,7 @@ int grow_slots(fwa_engine* e, int32_t add) {
         e->slot_ptr.push_back(base);
         e->touched.push_back(0);
         e->slot_clean.push_back(0);
+        e->stale.push_back(0);
         HIPCHK(e, hipMemsetAsync(base, 0, slot_bytes, e->stream));  // identities: 0; MIN columns 0xFF..
         for (int c = 1; c < e->nacc; ++c)
             if (e->ec.acc_kind[c] == ACC_MIN_ORD) HIPCHK(e, hipMemsetAsync(base + (int64_t)c * e->stride, 0xFF, col_bytes, e->stream));
@@ -2655,6 +2682,50 @@ int flush_resets(fwa_engine* e) {
     e->reset_launches++;
     e->pending_reset.clear();
     return FWA_OK;
+}
+
+// ---- stale retirement ----
+
+// May the tumbling fire retire a slot without identity stores? Only where the next push is expected to overwrite it:
+// a handle whose pushes run the two-phase ingest with neither PRE buckets nor window passes, without allowed lateness,
+// reduction, record lists, DISTINCT or DECIMAL layers (variant bit 9: identity stores as before, A/B; bit 0 takes the
+// fresh flags the overwrite rides on), and whose last settled push was such a push without a replay: a replay hands
+// slots to the v1 ingest, which needs them clean. The push decides again for itself (push_v2); a wrong guess costs a
+// reset.
+bool stale_eligible(const fwa_engine* e) {
+    return e->v2 && e->steady && e->kind == FWA_TUMBLE && !(e->opt_variant & (512 | 1)) && !e->pre && e->opt_pre != 1 && !e->mp &&
+           e->opt_mp != 1 && e->lateness == 0 && !e->red && !e->sparse && !e->dist && !e->dec && e->nacc == e->nacc_comb;
+}
+
+// Restore the identities of every stale slot (reset_slots_kernel) except those the pending push may overwrite. Called
+// ahead of everything that reads or accumulates into slots outside the two-phase push and the walking fire: the v1
+// ingest and its replays, the late-firing path, the other fires and the drains, partial rows, snapshot and restore.
+int clean_stale(fwa_engine* e) {
+    if (e->n_stale == 0) return FWA_OK;
+    for (int32_t s = 0; s < (int32_t)e->stale.size(); ++s) {
+        if (!e->stale[s]) continue;
+        bool pending = false;
+        for (auto& qs : e->push_stale) pending |= qs.second == s;
+        if (pending) continue;
+        e->stale[s] = 0;
+        e->n_stale--;
+        e->pending_reset.push_back(s);
+    }
+    return flush_resets(e);
+}
+
+// The status of a two-phase push is in h_st: its combiner has run, so the stale slots of the slices inside the slice
+// range of its Phase P are overwritten (the range combine3 read: min_q / max_q change only in a later replay). A push
+// that ended in an error leaves every mark.
+void settle_push_stale(fwa_engine* e) {
+    if (e->push_stale.empty()) return;
+    const DevStatus& st = *e->h_st;
+    if (!st.error && st.min_q != ~0ull) {
+        const int64_t q0 = jm::unord_i64(st.min_q), q1 = jm::unord_i64(st.max_q);
+        for (auto& qs : e->push_stale)
+            if (qs.first >= q0 && qs.first <= q1 && e->stale[qs.second]) { e->stale[qs.second] = 0; e->n_stale--; }
+    }
+    e->push_stale.clear();
 }
 
 int release_slot(fwa_engine* e, int32_t slot) {
@@ -3266,6 +3337,9 @@ static int ensure_iota(fwa_engine* e) {
 }
 
 static int launch_ingest(fwa_engine* e, IngestArgs& a, bool replay) {
+    // (a replay follows its push's combiner in the stream and its settle_push_stale: what is still stale was not
+    // overwritten, the slots alloc_slice just handed to the wanted slices included)
+    if (int rcs = clean_stale(e)) return rcs;
     if (e->dir_dirty) { int rc = publish_dir(e); if (rc) return rc; }
     if (e->iota_pending) { int rc = ensure_iota(e); if (rc) return rc; }
     a.spill_cap = e->spill_cap;
@@ -3379,12 +3453,27 @@ static int push_v2(fwa_engine* e, IngestArgs& a, bool* ran) {
     uint8_t* fresh = code + kRelCap;
     memset(fresh, 0, kRelCap);
     int64_t rel_hi = -1;                              // (rel_lo = 0: q_base is the first live slice)
+    const bool mp = e->opt_mp == 1 || (e->opt_mp != 0 && e->mp);   // combiner window passes (slices smaller than chunks)
+    // stale slots under the slices of this push: the combiner overwrites them (fresh 2) when it
+    // merges every slice of its window once and no other kernel writes slots first; otherwise they are reset here. Live
+    // slices past the tables reach their slots through the v1 replay only: reset too.
+    const bool lazy = !pre && !mp && !(e->opt_variant & (512 | 1));
+    e->push_stale.clear();
     for (auto& kv : e->live) {
         const int64_t rel = kv.first - q_base;
+        if (e->n_stale && e->stale[kv.second] && (!lazy || rel < 0 || rel >= kRelCap || e->touched[kv.second])) {
+            e->stale[kv.second] = 0;
+            e->n_stale--;
+            e->pending_reset.push_back(kv.second);
+        }
         if (rel < 0 || rel >= kRelCap) continue;
         rel_hi = rel;
         r2s[rel] = kv.second;
         fresh[rel] = (e->touched[kv.second] || (e->opt_variant & 1)) ? 0 : 1;   // variant bit 0: A/B without
+        if (e->n_stale && e->stale[kv.second]) {
+            fresh[rel] = 2;
+            e->push_stale.push_back({kv.first, kv.second});
+        }
         int64_t thr;
         bool always;
         accept_threshold(e, kv.first, &thr, &always);
@@ -3392,6 +3481,7 @@ static int push_v2(fwa_engine* e, IngestArgs& a, bool* ran) {
         else if (e->lateness > 0 && a.wm >= trig(e, jm::wsub(first_window_end(e, kv.first), 1))) code[rel] = kCodeSlow;
         else code[rel] = kCodeAccept;
     }
+    if ((rc = flush_resets(e))) return rc;
     if (rel_hi < kRelTabN && !(e->opt_variant & 256)) {   // a narrow span: the tables by value (variant bit 8: A/B)
         RelTab tab;
         memset(&tab, 0, sizeof(tab));
@@ -3487,7 +3577,6 @@ static int push_v2(fwa_engine* e, IngestArgs& a, bool* ran) {
     const bool narrow2 = e->opt_narrow != 0 && (e->opt_narrow == 1 || e->narrow) && layout == 0 && e->nv == 2 && vw == 1 &&
                          kgm == 0 && !pre && !a.pcount;
     e->narrow_used = narrow || narrow2;
-    const bool mp = e->opt_mp == 1 || (e->opt_mp != 0 && e->mp);   // combiner window passes (slices smaller than chunks)
 #define P3LAUNCH(NV, IT, VW) do { \
         if (kgm == 0) partition3_kernel<NV, IT, 1024, VW, 0><<<grid, 1024, 0, e->stream>>>(pa, e->d_ec); \
         else if (kgm == 1) partition3_kernel<NV, IT, 1024, VW, 1><<<grid, 1024, 0, e->stream>>>(pa, e->d_ec); \
@@ -3534,6 +3623,8 @@ static int push_v2(fwa_engine* e, IngestArgs& a, bool* ran) {
     // (not with PRE buckets: Phase P applies merged entries past a full sub-bucket to the slots with device atomics
     // before this merge -- tests/test_skew_gpu.py::test_pre_entries_past_bucket_end_applied_with_atomics)
     ca.relfresh = pre ? nullptr : (const uint8_t*)(e->d_rel2slot + kRelCap) + kRelCap;
+    ca.stale = e->push_stale.empty() ? 0 : 1;
+    ca.q_base = q_base;
     ca.slot_base = e->d_slot_base;
     ca.stride = e->stride;
     ca.st = e->d_st;
@@ -4033,7 +4124,30 @@ struct FireFuse {
     int64_t row0 = 0;
     bool check_st = false;
     std::vector<int32_t> cleared;   // out: the slots the kernel clears unless it finds the push unsettled
+    bool lazy = false;              // out: ... without storing identities: stale once the fire stands (fire_stands)
 };
+
+// The fire fu described stands (it was not discarded for an unsettled push): account what it retired. A pending push's
+// own stale slots must be settled first (settle_push_stale): this fire may have retired one of them again.
+static void fire_stands(fwa_engine* e, const FireFuse& fu) {
+    if (fu.cleared.empty()) return;
+    e->fused_fires++;
+    for (int32_t s : fu.cleared) {
+        if (fu.lazy) {
+            if (!e->stale[s]) { e->stale[s] = 1; e->n_stale++; }
+            e->stale_retires++;
+        } else if (e->stale[s]) {   // (a stale slot listed untouched: the fire stored its identities)
+            e->stale[s] = 0;
+            e->n_stale--;
+        }
+    }
+}
+
+// Would enqueue_fire send these windows through fire_walk_kernel?
+static bool walk_fire_ok(const fwa_engine* e, const std::vector<FireWindow>& hw) {
+    return !e->red && e->kind == FWA_TUMBLE && !(e->opt_variant & 256) && e->nacc >= 1 && e->nacc <= 5 && !hw.empty() &&
+           (int)hw.size() <= kWalkMaxWin && std::all_of(hw.begin(), hw.end(), [](const FireWindow& w) { return w.nslots == 1; });
+}
 
 // d_st->rows = 0 ahead of a fire: push_reset_kernel already did it unless something fired since the last push.
 static int zero_rows(fwa_engine* e) {
@@ -4061,6 +4175,8 @@ static int enqueue_fire_walk(fwa_engine* e, const std::vector<FireWindow>& hw, c
     // (a) every row fits: windows x keys, the pending push's records counted as new keys
     const int64_t nk = std::min<int64_t>(e->capacity + 1, (int64_t)e->h_st->n_keys + (e->pend ? e->pend_n : 0));
     const bool fits = fu && fu->wm != LONG_MIN_J && fu->row0 + (int64_t)hw.size() * std::max<int64_t>(nk, 1) <= e->out_cap;
+    const bool lazy = stale_eligible(e);
+    if (fu) fu->lazy = lazy;
     for (size_t i = 0; i < hw.size(); ++i) {
         WalkWin& w = f.win[i];
         w.start = hw[i].start;
@@ -4070,8 +4186,14 @@ static int enqueue_fire_walk(fwa_engine* e, const std::vector<FireWindow>& hw, c
         int64_t thr;
         bool always;
         accept_threshold(e, slice_q(e, w.start), &thr, &always);
-        w.retire = fits && !always && fu->wm >= thr ? 1 : 0;   // (c) as retire_slices: fired but still accepting stays
+        w.retire = fits && !always && fu->wm >= thr ? (lazy ? 2 : 1) : 0;   // (c) as retire_slices: fired but still accepting stays
         if (w.retire) fu->cleared.push_back(w.slot);
+        if (e->n_stale && e->stale[w.slot]) {   // listed untouched by a speculative fire: holds values only if the
+            w.gate = 2;                         // pending push overwrites it
+            f.gated = 1;
+            for (auto& qs : e->push_stale)
+                if (qs.second == w.slot) { w.gate = 1; w.qord = jm::ord_i64(qs.first); }
+        }
     }
     // 8 kids per thread for one or two columns, 4 for more (r07: 2 and 4 kids per thread measured 349 and 198 us per
     // C2 fire against 182 at 8; 16 kids, 217 VGPRs, the same as 8)
@@ -4092,8 +4214,7 @@ static int enqueue_fire(fwa_engine* e, const std::vector<FireWindow>& hw, const 
                         FireFuse* fu = nullptr) {
     e->rows_zero = false;
     if (fu) fu->cleared.clear();
-    if (!raw && !e->red && e->kind == FWA_TUMBLE && !(e->opt_variant & 256) && e->nacc >= 1 && e->nacc <= 5 && !hw.empty() &&
-        (int)hw.size() <= kWalkMaxWin && std::all_of(hw.begin(), hw.end(), [](const FireWindow& w) { return w.nslots == 1; })) {
+    if (!raw && walk_fire_ok(e, hw)) {
         HIPCHK(e, hipEventRecord(e->ev[2], e->stream));
         int rc = enqueue_fire_walk(e, hw, hs, fu);
         if (rc) return rc;
@@ -4101,6 +4222,7 @@ static int enqueue_fire(fwa_engine* e, const std::vector<FireWindow>& hw, const 
         HIPCHK(e, hipEventRecord(e->ev[3], e->stream));
         return FWA_OK;
     }
+    if (int rc = clean_stale(e)) return rc;   // (no push is pending here with stale slots: speculative_fire)
     if (int rc = upload_windows(e, hw, hs)) return rc;
     FireArgs f;
     memset(&f, 0, sizeof(f));
@@ -4190,7 +4312,8 @@ static int launch_fire(fwa_engine* e, const std::vector<FireWindow>& hw, const s
     if (rc) return rc;
     rc = sync_status(e);   // (the touched mirror comes back with the flags the fire cleared)
     if (rc) return rc;
-    if (!fu.cleared.empty() && !(fu.check_st && (e->h_st->spill_n || e->h_st->late_fire || e->h_st->error))) e->fused_fires++;
+    if (fu.check_st) settle_push_stale(e);   // the pending push's status came back with the fire's
+    if (!(fu.check_st && (e->h_st->spill_n || e->h_st->late_fire || e->h_st->error))) fire_stands(e, fu);
     *nrows = (int64_t)e->h_st->rows;
     if (*nrows > e->out_cap) {   // more rows than the first sizing: grow (2x headroom for the following
         rc = ensure_out(e, std::max<int64_t>(*nrows, std::min<int64_t>(bound, 2 * *nrows)));   // fires), fire again
@@ -4229,6 +4352,7 @@ static int ensure_late_rows(fwa_engine* e, int64_t need) {
 // and emit the fired windows' contents into the late-row buffer (late_fire_kernel). The rows are returned
 // by the next fwa_advance_watermark, ahead of the windows that watermark fires.
 static int process_late(fwa_engine* e, const IngestArgs& a0, std::vector<int32_t>& idx) {
+    if (int rcs = clean_stale(e)) return rcs;
     std::sort(idx.begin(), idx.end());
     const int64_t n = (int64_t)idx.size();
     if (n > e->spill_cap) return fail(e, FWA_E_STATE, "late list overflow");
@@ -4378,6 +4502,7 @@ static int push_common(fwa_engine* e, IngestArgs& a, int64_t n, bool allow_v2, b
     if (++e->push_epoch == INT32_MAX) { e->push_epoch = 1; e->rs_valid = false; }   // (epochs wrap: carried sums dropped)
     int rc = FWA_OK;
     bool ran_v2 = false;
+    e->push_stale.clear();   // (left by a push that failed: its marks stay)
     if (e->v2 && allow_v2) {
         rc = push_v2(e, a, &ran_v2);
         if (rc) return rc;
@@ -4430,6 +4555,7 @@ static int push_settle(fwa_engine* e, IngestArgs& a, int64_t n, bool ran_v2, boo
         if (ran_v2 && round == 0 && (int64_t)st.strag_n * 64 > n) e->mp = true;  // wide chunks: window passes
         if (ran_v2 && round == 0) e->stragglers += st.strag_n;
         if (ran_v2 && round == 0 && e->narrow_used && (int64_t)st.wide_n * 64 > n) e->narrow = false;   // 64-bit keys / values
+        if (round == 0) settle_push_stale(e);
         if (st.error) {
             const char* m = st.error == FWA_E_KEYGROUP ? "Key group is not in the owned KeyGroupRange (StateTable.getMapForKeyGroup)"
                           : st.error == FWA_E_TS_MIN ? "Record has Long.MIN_VALUE timestamp (= no timestamp marker)."
@@ -4445,6 +4571,7 @@ static int push_settle(fwa_engine* e, IngestArgs& a, int64_t n, bool ran_v2, boo
         dropped += (int64_t)st.dropped;
         if (st.max_q) qmax = std::max<int64_t>(qmax, jm::unord_i64(st.max_q));
         if (st.min_q != ~0ull) qmin = std::min<int64_t>(qmin, jm::unord_i64(st.min_q));
+        if (round == 0) e->steady = ran_v2 && st.spill_n == 0;
         if (st.spill_n == 0) break;
         if (round > 64) return fail(e, FWA_E_STATE, "miss replay did not converge");
         // allocate the wanted slices, republish, replay the missed records
@@ -4808,6 +4935,7 @@ int fwa_drain_route(fwa_engine* e, int64_t wm, int32_t parallelism, fwa_routed* 
     e->rs_valid = false;
     HIPCHK(e, hipSetDevice(e->cfg.device));
     if (int rc0 = settle_pending(e)) return rc0;
+    if (int rcs = clean_stale(e)) return rcs;
     // the previous call's blocks may still be read on the input stream (the exchange's all-to-all): the drain
     // rewrites them only after everything enqueued there
     if (int rc0 = wait_input_stream(e)) return rc0;
@@ -4916,6 +5044,7 @@ int fwa_fire_partials(fwa_engine* e, const int64_t* rows, int64_t n, int32_t m, 
     if (int rcf = finish_afire(e)) return rcf;
     e->af_pend = false;
     if (int rc0 = settle_pending(e)) return rc0;
+    if (int rcs = clean_stale(e)) return rcs;
     // the merge-fire path: every window merged here fires at wm and nothing else is held (TUMBLE, no lateness,
     // no live slice with data); the redo through the defining calls covers every row it cannot place
     bool fast = e->opt_fire_partials != 0 && n > 0 && (flags & FWA_PUSH_DEVICE_PTRS) && !e->sparse && !e->red &&
@@ -5070,6 +5199,7 @@ int fwa_drain_partials(fwa_engine* e, int64_t wm, fwa_partials* out) {
     if (e->kind == FWA_SESSION) return fail(e, FWA_E_UNSUPPORTED, "partial accumulators need a slicing window");
     HIPCHK(e, hipSetDevice(e->cfg.device));
     if (int rc0 = settle_pending(e)) return rc0;
+    if (int rcs = clean_stale(e)) return rcs;
     if (int rc0 = wait_input_stream(e)) return rc0;   // device columns of the last drain may still be read there
     memset(out, 0, sizeof(*out));
     std::vector<FireWindow> hw;
@@ -5332,6 +5462,7 @@ int fwa_snapshot(fwa_engine* e, fwa_blob* out) {
         return fail(e, FWA_E_UNSUPPORTED, "snapshot of PREHASHED keys in record lists");
     HIPCHK(e, hipSetDevice(e->cfg.device));
     if (int rc0 = settle_pending(e)) return rc0;
+    if (int rcs = clean_stale(e)) return rcs;
     if (e->kind == FWA_SESSION) return snapshot_sessions(e, out);
     std::vector<FireWindow> hw;
     std::vector<int32_t> hs;
@@ -5428,6 +5559,7 @@ int fwa_restore(fwa_engine* e, const void* const* blobs, const int64_t* sizes, i
     if (!e) return FWA_E_STATE;
     if (n_blobs < 0 || (n_blobs > 0 && (!blobs || !sizes))) return fail(e, FWA_E_ARG, "null snapshot list");
     if (int rc0 = settle_pending(e)) return rc0;
+    if (int rcs = clean_stale(e)) return rcs;
     if (e->records_in != 0 || e->wm != LONG_MIN_J || !e->live.empty() || e->n_ss != 0 || sp_live_windows(e) != 0)
         return fail(e, FWA_E_STATE, "restore needs a fresh handle");
     const int na = e->cfg.num_aggs, maxp = e->cfg.max_parallelism, nh = e->ec.naggs - e->ec.nout;
@@ -5660,6 +5792,9 @@ static int speculative_fire(fwa_engine* e, int64_t wm, int64_t* nrows, bool* ok)
         hw.push_back(f);
     }
     int rc = FWA_OK;
+    // (another fire kernel reads every listed slot as it is: with stale slots about, settle first and fire what the
+    // settled flags list -- the caller's path)
+    if (e->n_stale && !walk_fire_ok(e, hw)) return settle_pending(e);
     if (!hw.empty()) {
         rc = launch_fire(e, hw, hs, 0, nrows, 0, wm);   // synchronises: the push's status is in h_st too
         if (rc) return rc;
@@ -5866,7 +6001,7 @@ int fwa_advance_watermark_async(fwa_engine* e, int64_t wm) {
         // its rows and sizes them instead.
         const int64_t nk = std::min<int64_t>(e->capacity + 1, (int64_t)e->h_st->n_keys + e->pend_n);
         const int64_t need = (int64_t)hw.size() * std::max<int64_t>(nk, 1);
-        if (!hw.empty() && (need <= e->out_cap || wm != LONG_MAX_J)) {
+        if (!hw.empty() && (need <= e->out_cap || wm != LONG_MAX_J) && (!e->n_stale || walk_fire_ok(e, hw))) {
             int rc = ensure_out(e, need);
             if (rc) return rc;
             FireFuse fu;
@@ -5883,7 +6018,8 @@ int fwa_advance_watermark_async(fwa_engine* e, int64_t wm) {
                 e->af_pend = true;
                 // slots the fire cleared itself: the mirror just read predates the fire
                 for (int32_t s : fu.cleared) e->touched[s] = 0;
-                if (!fu.cleared.empty()) e->fused_fires++;
+                settle_push_stale(e);
+                fire_stands(e, fu);
                 if ((rc = retire_slices(e, wm))) return rc;   // the other resets, enqueued behind the fire
                 if ((rc = settle_push(e))) return rc;      // no wait (st_ready)
                 e->wm = wm;
@@ -6013,6 +6149,7 @@ int fwa_get_option(const fwa_engine* e, int32_t option, int64_t* value) {
         case FWA_OPT_DEC_WRAP_NULL: *value = e->opt_dec_wrap_null; return FWA_OK;
         case FWA_OPT_FUSED_FIRES: *value = e->fused_fires; return FWA_OK;
         case FWA_OPT_RESET_LAUNCHES: *value = e->reset_launches; return FWA_OK;
+        case FWA_OPT_STALE_RETIRES: *value = e->stale_retires; return FWA_OK;
         case FWA_OPT_STRAGGLERS: *value = e->stragglers; return FWA_OK;
         case FWA_OPT_KEY_TABLE_DIGEST: {   // FNV-1a over the table's words in slot order (the side slot included)
             std::vector<unsigned long long> table((size_t)e->capacity + 1);

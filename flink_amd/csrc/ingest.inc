@@ -893,7 +893,15 @@ struct CombineArgs {
     int32_t seg_log, np, sl;           // sl: LDS slice window
     int32_t sub_major;                 // bucket layout (bucket_base)
     const int32_t* rel2slot;           // [kRelCap]
-    const uint8_t* relfresh;           // [kRelCap] 1: the slot still holds its identities (no record reached it yet)
+    const uint8_t* relfresh;           // [kRelCap] 1: the slot still holds its identities (no record reached it yet);
+                                       // 2: a stale slot (below), as fresh as 1 to the merge
+    // Stale retirement (DESIGN.md §5): a slot the tumbling fire retired without storing identities still holds the
+    // fired window's values. The slices of this push that sit on such slots have relfresh 2; those inside the push's
+    // slice range (DevStatus min_q .. max_q of Phase P, final when this kernel starts) leave it clean: a block's merge
+    // of such a slice stores every kid of its segment, and the block stores identities over its segment for the ones
+    // it never merges. Stale slices outside the range are not written and stay stale (the host reads the same range).
+    int32_t stale;                     // 1: some relfresh entry is 2
+    int64_t q_base;                    // slice number of rel 0
     unsigned long long* key_table;
     unsigned long long* const* slot_base;
     int64_t stride;
@@ -940,6 +948,73 @@ __device__ __forceinline__ void strag_apply(const CombineArgs& a, const EngineCo
         }
     }
 }
+
+// Stale retirement: the push's slice range as relative slices [lo, hi] (hi < lo: nothing to clean).
+__device__ __forceinline__ void stale_range(const CombineArgs& a, int& lo, int& hi) {
+    lo = 0;
+    hi = -1;
+    if (!a.stale) return;
+    const unsigned long long mn = a.st->min_q, mx = a.st->max_q;
+    if (mn == ~0ull) return;
+    lo = (int)(jm::unord_i64(mn) - a.q_base);
+    hi = (int)(jm::unord_i64(mx) - a.q_base);
+}
+
+// ... and identities over kids [k0, k1) of the slot of relative slice rel, every column (k0, k1 even: 16-byte stores).
+// kind_of(cc): the accumulator kind of column cc > 0.
+template <int TH, class F>
+__device__ __forceinline__ void stale_ident(const CombineArgs& a, int rel, int64_t k0, int64_t k1, int tid, int nacc, F&& kind_of) {
+    const int32_t slot = a.rel2slot[rel];
+    if (slot < 0) return;
+    const int64_t n2 = (k1 - k0) / 2;
+    for (int cc = 0; cc < nacc; ++cc) {
+        const unsigned long long id = cc == 0 ? 0ull : ident_of(kind_of(cc));
+        ulonglong2* col = (ulonglong2*)(a.slot_base[slot] + (int64_t)cc * a.stride + k0);
+        for (int64_t i = tid; i < n2; i += TH) col[i] = make_ulonglong2(id, id);
+    }
+}
+
+// The kids behind the partitions (np << seg_log .. stride - 1: the side slot of the INT64_MIN key and the padding) belong
+// to no combiner block and are written by the v1 path only, in a later kernel: the last block restores them up front.
+template <int TH, class F>
+__device__ __forceinline__ void stale_side(const CombineArgs& a, int lo, int hi, int tid, int nacc, F&& kind_of) {
+    for (int r = lo; r <= hi; ++r)
+        if (a.relfresh[r] == 2) stale_ident<TH>(a, r, (int64_t)a.np << a.seg_log, a.stride, tid, nacc, kind_of);
+}
+
+// A block merges the slices [first lo, last lo + SL) of its window, each once and in order (no window passes), and its
+// stragglers are older than the window: records of a slice below the first lo, or of one already merged. The first lo
+// is the oldest slice of the block's first chunk (every wave's list starts there). So, ahead of the chunk loop, the
+// stale slices below it get their identities, with a barrier ahead of any straggler's atomics (a full straggler list
+// applies them at once) -- all of the range when the partition got no entry; the stale slices inside the window's path
+// are stored whole by their merge, which a barrier separates from the later stragglers as ever; and the ones above the
+// last window get their identities on exit.
+// (lo, ident_seg, s_first, the first chunk's nrel: the bodies' locals. The conditions are uniform over the block. The
+// range is read again at each use: nothing of this stays in registers across the chunk loop. WMIN: the wave's minimum
+// of an unsigned value, in lane 0 at least.)
+#define STALE_BELOW(WMIN) do { \
+        if (a.stale) { \
+            uint32_t m_ = 0x7fffffffu; \
+            for (int j_ = 0; j_ < IT; ++j_) m_ = min(m_, (uint32_t)nrel[j_]);   /* (an invalid entry's -1: the largest) */ \
+            m_ = WMIN(m_); \
+            if (lane == 0) atomicMin(&s_first, (int)m_); \
+            __syncthreads(); \
+            int s_lo_, s_hi_; \
+            stale_range(a, s_lo_, s_hi_); \
+            const int first_ = s_first; \
+            for (int r_ = s_lo_; r_ <= s_hi_ && r_ < first_; ++r_) if (a.relfresh[r_] == 2) ident_seg(r_); \
+            __syncthreads(); \
+        } } while (0)
+#define STALE_ABOVE() do { \
+        if (lo != 0x7fffffff) { \
+            int s_lo_, s_hi_; \
+            stale_range(a, s_lo_, s_hi_); \
+            for (int r_ = max(s_lo_, lo + SL); r_ <= s_hi_; ++r_) if (a.relfresh[r_] == 2) ident_seg(r_); \
+        } } while (0)
+#define STALE_SIDE(NACC) do { \
+        int s_lo_, s_hi_; \
+        stale_range(a, s_lo_, s_hi_); \
+        if (p == a.np - 1) stale_side<TH>(a, s_lo_, s_hi_, tid, NACC, kind_of); } while (0)
 
 // Stragglers of one combiner block, kept in LDS and applied after the block's last merge.
 constexpr int kStragL = 256;
@@ -1083,7 +1158,7 @@ __device__ __forceinline__ void combine3_lean(const CombineArgs& a, const Engine
     const int seg = 1 << a.seg_log;
     const uint32_t smask = (uint32_t)seg - 1u;
     __shared__ StragL s_strag[kStragL];
-    __shared__ int s_sn;
+    __shared__ int s_sn, s_first;
     // LDS, at the general body's offsets (push_v2 sizes one block for both): key image [seg] i32 (swizzled, kswz32),
     // COUNT [SL][seg] u32, SUM [SL][seg] u64, s_mm: the block's slice range of a chunk {min, max} x 3 (below), s_new
     int32_t* lkey = (int32_t*)smem;
@@ -1097,7 +1172,7 @@ __device__ __forceinline__ void combine3_lean(const CombineArgs& a, const Engine
     unsigned long long* gkeys = a.key_table + ((int64_t)p << a.seg_log);
     for (int i = tid; i < seg; i += TH) lkey[kswz32((uint32_t)i)] = lean_key_image(gkeys[i]);
     for (int i = tid; i < SL * seg; i += TH) { lcnt[i] = 0; lacc[i] = 0ull; }
-    if (tid == 0) { *s_new = 0; s_sn = 0; }
+    if (tid == 0) { *s_new = 0; s_sn = 0; s_first = 0x7fffffff; }
     if (tid < 3) { s_mm[2 * tid] = 0x7fffffff; s_mm[2 * tid + 1] = -1; }
     constexpr int64_t kChunk = (int64_t)IT * 64;
     // (the wave's own count, as a scalar: whole chunks are loaded without a bounds test per entry)
@@ -1108,12 +1183,20 @@ __device__ __forceinline__ void combine3_lean(const CombineArgs& a, const Engine
     const gc_u64_ptr bk = (const gc_u64_ptr)(a.b_key + boff);
     const __attribute__((address_space(1))) uint16_t* br = (const __attribute__((address_space(1))) uint16_t*)(a.b_rel + boff);
     int lo = 0x7fffffff;
+    // stale retirement (CombineArgs): a stale slice is stored whole by its merge
+    auto kind_of = [](int) { return (int)ACC_ADD_I64; };
+    auto ident_seg = [&](int r) { stale_ident<TH>(a, r, (int64_t)p << a.seg_log, ((int64_t)p + 1) << a.seg_log, tid, 2, kind_of); };
+    STALE_SIDE(2);
     auto flush = [&](int rel) {   // merge window slice `rel` into HBM (the general body's flush for COUNT + one ADD_I64)
         constexpr int kPer = 4096 / TH;   // seg <= 4096
         const int w = rel & (SL - 1);
         const int32_t slot = (rel >= 0 && rel < kRelCap) ? a.rel2slot[rel] : -1;
         g_u64* base = slot >= 0 ? (g_u64*)a.slot_base[slot] : nullptr;
-        const bool fresh = slot >= 0 && a.relfresh && a.relfresh[rel];
+        const int fr = (slot >= 0 && a.relfresh) ? (int)a.relfresh[rel] : 0;
+        const bool fresh = fr != 0;
+        // stale: every kid, the ones without a count too (a slice past the push's range, in the last window of a push of
+        // fewer than SL slices, gets identities it did not need; the host keeps it stale)
+        const bool all = fr == 2;
         uint32_t k[kPer];
         unsigned long long x[kPer];
         int64_t g[kPer];
@@ -1134,7 +1217,8 @@ __device__ __forceinline__ void combine3_lean(const CombineArgs& a, const Engine
             old1[m] = (k[m] && !fresh) ? col[g[m]] : 0ull;
         }
 #pragma unroll
-        for (int m = 0; m < kPer; ++m) if (k[m]) { base[g[m]] = old[m] + k[m]; col[g[m]] = old1[m] + x[m]; }
+        for (int m = 0; m < kPer; ++m)
+            if (k[m] || (all && tid + m * TH < seg)) { base[g[m]] = old[m] + k[m]; col[g[m]] = old1[m] + x[m]; }
     };
     __syncthreads();
     // register double buffer: n* = chunk in flight, the packed entries (key | value << 32) are unpacked at use
@@ -1157,6 +1241,9 @@ __device__ __forceinline__ void combine3_lean(const CombineArgs& a, const Engine
         }
     };
     load_chunk(0);
+#define STALE_WMIN(x) (uint32_t)lean_wave_red<false>((int)(x))
+    STALE_BELOW(STALE_WMIN);
+#undef STALE_WMIN
     PMARK(0);
     int it = 0;
     for (int64_t cb = 0; cb < cnt; cb += kChunk, ++it) {
@@ -1299,6 +1386,7 @@ __device__ __forceinline__ void combine3_lean(const CombineArgs& a, const Engine
     __syncthreads();
     if (lo != 0x7fffffff)
         for (int r = lo; r < lo + SL; ++r) flush(r);
+    STALE_ABOVE();
     __syncthreads();                    // every merge of this block stored before the stragglers' atomics
     if (tid == 0 && s_sn) atomicAdd(&a.st->strag_n, s_sn);
     for (int t = tid; t < min(s_sn, kStragL); t += TH) {
@@ -1344,7 +1432,7 @@ __global__ void __launch_bounds__(TH, 1) combine3_kernel(CombineArgs a, const En
     const int nacc = LAYOUT == 1 ? 2 : (LAYOUT == 2 ? 1 : c.nacc_comb);
     __shared__ int s_desc[kMaxAggsInt + 1];   // generic layout: per column kind | vslot << 8 | input kind << 16
     __shared__ StragL s_strag[kStragL];
-    __shared__ int s_sn;
+    __shared__ int s_sn, s_first;
     if (LAYOUT == 0 && tid == 0) {
         for (int j = 0; j < c.naggs; ++j)
             if (c.agg[j].acc > 0 && !c.agg[j].alias) s_desc[c.agg[j].acc] = c.agg[j].acc_kind | (c.agg[j].vslot << 8) | (c.agg[j].kind << 16);
@@ -1364,7 +1452,7 @@ __global__ void __launch_bounds__(TH, 1) combine3_kernel(CombineArgs a, const En
     unsigned long long* gkeys = a.key_table + ((int64_t)p << a.seg_log);
     for (int i = tid; i < seg; i += TH) lkey[kswz((uint32_t)i)] = gkeys[i];
     for (int i = tid; i < SL * seg; i += TH) lcnt[i] = 0;
-    if (tid == 0) { *s_new = 0; s_sn = 0; }
+    if (tid == 0) { *s_new = 0; s_sn = 0; s_first = 0x7fffffff; }
     __syncthreads();
     for (int cc = 1; cc < nacc; ++cc) {
         const unsigned long long id = LAYOUT == 1 ? 0ull : ident_of(s_desc[cc] & 0xff);
@@ -1382,6 +1470,12 @@ __global__ void __launch_bounds__(TH, 1) combine3_kernel(CombineArgs a, const En
     const __attribute__((address_space(1))) uint16_t* br = (const __attribute__((address_space(1))) uint16_t*)(a.b_rel + boff);
     const __attribute__((address_space(1))) uint16_t* bn = PRE ? (const __attribute__((address_space(1))) uint16_t*)(a.b_n + boff) : nullptr;
     int lo = 0x7fffffff;
+    // stale retirement (CombineArgs; the host sets it for neither PRE buckets nor window passes): a stale slice is
+    // stored whole by its merge
+    constexpr bool kStale = !PRE && !MP;
+    auto kind_of = [&](int cc) { return LAYOUT == 1 ? (int)ACC_ADD_I64 : (s_desc[cc] & 0xff); };
+    auto ident_seg = [&](int r) { stale_ident<TH>(a, r, (int64_t)p << a.seg_log, ((int64_t)p + 1) << a.seg_log, tid, nacc, kind_of); };
+    if constexpr (kStale) STALE_SIDE(nacc);
     auto flush = [&](int rel) {   // merge window slice `rel` into HBM; every thread owns seg/TH slots
         constexpr int kPer = 4096 / TH;   // seg <= 4096
         const int w = rel & (SL - 1);
@@ -1390,7 +1484,9 @@ __global__ void __launch_bounds__(TH, 1) combine3_kernel(CombineArgs a, const En
         // a slot no record reached before this push holds its identities, and this block merges each of its slices
         // once (later entries of the slice straggle, applied after the last merge; the host passes no flags when Phase P
         // may have written slots itself, PRE): store without reading
-        const bool fresh = slot >= 0 && a.relfresh && a.relfresh[rel];
+        const int fr = (slot >= 0 && a.relfresh) ? (int)a.relfresh[rel] : 0;
+        const bool fresh = fr != 0;
+        const bool all = kStale && fr == 2;   // stale: every kid, identities where no count (the lean body's note)
         uint32_t k[kPer];
         int64_t g[kPer];
 #pragma unroll
@@ -1405,7 +1501,7 @@ __global__ void __launch_bounds__(TH, 1) combine3_kernel(CombineArgs a, const En
 #pragma unroll
             for (int m = 0; m < kPer; ++m) old[m] = (k[m] && !fresh) ? base[g[m]] : 0ull;
 #pragma unroll
-            for (int m = 0; m < kPer; ++m) if (k[m]) base[g[m]] = old[m] + k[m];
+            for (int m = 0; m < kPer; ++m) if (k[m] || (all && tid + m * TH < seg)) base[g[m]] = old[m] + k[m];
         }
         for (int cc = 1; cc < nacc; ++cc) {
             const int akc = LAYOUT == 1 ? ACC_ADD_I64 : (s_desc[cc] & 0xff);
@@ -1427,7 +1523,10 @@ __global__ void __launch_bounds__(TH, 1) combine3_kernel(CombineArgs a, const En
             for (int m = 0; m < kPer; ++m) old[m] = (k[m] && !fresh) ? col[g[m]] : id;
 #pragma unroll
             for (int m = 0; m < kPer; ++m) {
-                if (!k[m]) continue;
+                if (!k[m]) {
+                    if (all && tid + m * TH < seg) col[g[m]] = id;
+                    continue;
+                }
                 unsigned long long r = old[m];
                 switch (akc) {
                     case ACC_ADD_I64: r = old[m] + x[m]; break;
@@ -1465,6 +1564,10 @@ __global__ void __launch_bounds__(TH, 1) combine3_kernel(CombineArgs a, const En
         }
     };
     load_chunk(0);
+    if constexpr (kStale) {
+        auto wmin = [](uint32_t x) { for (int sh = 32; sh >= 1; sh >>= 1) x = min(x, (uint32_t)__shfl_xor((int)x, sh)); return x; };
+        STALE_BELOW(wmin);
+    }
     PMARK(0);
     int it = 0;
     for (int64_t cb = 0; cb < cnt; cb += kChunk, ++it) {
@@ -1610,6 +1713,7 @@ __global__ void __launch_bounds__(TH, 1) combine3_kernel(CombineArgs a, const En
     __syncthreads();
     if (lo != 0x7fffffff)
         for (int r = lo; r < lo + SL; ++r) flush(r);
+    if constexpr (kStale) STALE_ABOVE();
     __syncthreads();                    // every merge of this block stored before the stragglers' atomics
     if (tid == 0 && s_sn) atomicAdd(&a.st->strag_n, s_sn);
     for (int t = tid; t < min(s_sn, kStragL); t += TH) {

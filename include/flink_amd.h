@@ -629,7 +629,9 @@ enum fwa_option {
                                     tumbling fire as one kernel block per (window, key chunk) with an uploaded window
                                     table, a memset of its row counter and reset_slots_kernel for the retired slots,
                                     instead of the one-pass fire that retires its slots itself, and every push uploads
-                                    its slice tables instead of passing narrow ones in the kernel arguments */
+                                    its slice tables instead of passing narrow ones in the kernel arguments; bit 9
+                                    (512): the one-pass tumbling fire stores the identities over the slots it retires
+                                    instead of leaving them stale for the next two-phase push to overwrite */
     FWA_OPT_SLIDE_CARRIED = 13,  /* read only: sliding fires whose first window reused the previous run's carried
                                     window sums (fwa_get_option; set: 0 disables the reuse, 1 enables it, default) */
     FWA_OPT_FIRE_PARTIALS = 14,  /* read only: fwa_fire_partials calls that merged and fired on chip (fwa_get_option;
@@ -656,7 +658,9 @@ enum fwa_option {
                                        fwa_stats.fire_ms) */
     FWA_OPT_DISTINCT_COUNT_US = 24, /* read only, the same handles: ... and scanning the set for the counts (session
                                        mode: the clear of the fired sessions' bits included) */
-    FWA_OPT_DISTINCT_COUNT_STEPS = 25 /* read only, the same handles: firing steps counted so far */
+    FWA_OPT_DISTINCT_COUNT_STEPS = 25, /* read only, the same handles: firing steps counted so far */
+    FWA_OPT_STALE_RETIRES = 26   /* read only: slots the tumbling fire retired without storing their identities, left
+                                    for the next two-phase push to overwrite (fwa_get_option) */
 };
 int fwa_set_option(fwa_engine* e, int32_t option, int64_t value);
 /* The option's effective value: for the tri-state options 1 if the handle currently takes that path (forced, or
