@@ -25,6 +25,11 @@
 // into Arrow-style offsets (device scan) and bytes (gather from the still-resident wire bytes) on demand. The
 // fixed-length instantiation is the code as it was.
 //
+// Rows with non-compact DECIMAL fields (FWA_FIELD_DECIMAL) vary in length too (16 reserved bytes per non-NULL one, or
+// per field in the writeDecimal(null) form) and take the VAR scan; their decode pass is a third instantiation (DEC),
+// in which the record's lane checks each DECIMAL column's slot against the row, assembles the big-endian bytes in LDS
+// and stores the sign-extended 128-bit value with one 16-byte store. Schemas without one run the kernels they ran.
+//
 // HBM traffic: the wire bytes are read twice (scan, decode), the maps are S x 4 B per 4 KiB chunk, the
 // columns are written once. Bound: HBM (wire decoder).
 //
@@ -64,6 +69,7 @@ struct WireConst {
     int32_t row_size, nullbits;        // ROWDATA: BinaryRowData size (fixed part only) and null-bit-set width
     int32_t nstr;                      // STRING fields (> 0: records vary in length, the VAR kernels run)
     int32_t str_field[FWA_WIRE_MAX_FIELDS];
+    int32_t ndecf, ndec;               // DECIMAL fields (> 0: VAR as well) and how many of them are value columns
 };
 
 struct WireStatus {
@@ -94,6 +100,7 @@ struct Lds {
 };
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
 constexpr int kBufWords = (kChunk + kMaxStep + 3 + 8 + 3) / 4;
 
 // Copy bytes [0, lim) of src (a chunk start: 4 KiB-aligned offset into the input) into LDS.
@@ -439,6 +446,7 @@ struct DecodeOut {
 
 constexpr int kErrTooLong = 512;       // WireStatus.err_tag of an element over the ceiling (>= 256: RowKind + 256)
 constexpr int kErrSlot = 513;          // ... of a STRING slot pointing outside its row
+constexpr int kErrDecSlot = 514;       // ... of a DECIMAL slot: bytes outside the row's variable-length part, 0 or > 16 of them
 
 __device__ void raise_err(WireStatus* st, int code, int tag, int64_t pos) {
     if (atomicCAS(&st->error, 0, code) == 0) {
@@ -469,8 +477,10 @@ __device__ __forceinline__ bool field_null(const Lds& b, int row, int f) {   // 
 
 // ---- decode: persistent 64-lane blocks; the chunk's true chain is walked from its resolved entry and every
 // element is decoded by the lane that confirmed it. VAR: element_at has already checked the row's size int and
-// RowKind; every STRING slot is checked against the row here, before anything reads the value's bytes ----
-template <bool VAR>
+// RowKind; every STRING slot is checked against the row here, before anything reads the value's bytes.
+// DEC (with VAR): the schema has DECIMAL value columns; their slots are checked the same way, then the 1..16 big-endian
+// bytes (inside the row, so inside the staged chunk and its halo) are read from LDS by the record's lane ----
+template <bool VAR, bool DEC = false>
 __global__ __launch_bounds__(64) void wire_decode_kernel(const uint8_t* __restrict__ in, int64_t nbytes, int64_t nchunks,
                                                           WireConst w, bool aligned, const uint8_t* __restrict__ c_ent,
                                                           const uint64_t* __restrict__ c_rec,
@@ -536,6 +546,32 @@ __global__ __launch_bounds__(64) void wire_decode_kernel(const uint8_t* __restri
                 o.ts[g] =w.ts_field >= 0 ? (int64_t)read_field(b, q, w.ts_field, w) : ts;
                 for (int j = 0; j < w.num_cols; ++j) {
                     const int f = w.col_field[j];
+                    if constexpr (DEC) {
+                        if (w.ftype[f] == FWA_FIELD_DECIMAL) {
+                            // BinarySegmentUtils.readDecimalData: new BigInteger(the slot's `len` bytes). The reader
+                            // asks neither for the minimal length nor for 16 bytes inside the row; a NULL field's slot
+                            // is not looked at (setNullAt leaves 0, writeDecimal(null) leaves cursor << 32)
+                            uint64_t lo = 0, hi = 0;
+                            if (!field_null(b, q, f)) {
+                                const uint64_t slot = b.le64(q + w.foff[f]);
+                                const uint64_t off = slot >> 32, ln = slot & 0xffffffffull;
+                                const uint64_t size = (uint64_t)b.be32(q - 4);      // the row's size int (<= 249)
+                                if (off < (uint64_t)w.row_size || off + ln > size || ln < 1 || ln > 16)
+                                    raise_err(o.st, FWA_E_CORRUPT, kErrDecSlot, cs + p);
+                                else {
+                                    const int at = q + (int)off;
+                                    lo = hi = (b.byte(at) & 0x80) ? ~0ull : 0ull;   // sign extension from the first byte
+                                    for (int i = 0; i < (int)ln; ++i) {
+                                        hi = (hi << 8) | (lo >> 56);
+                                        lo = (lo << 8) | b.byte(at + i);
+                                    }
+                                }
+                            }
+                            const u64x2 v128 = {lo, hi};
+                            reinterpret_cast<u64x2*>(o.col[j])[g] = v128;
+                            continue;
+                        }
+                    }
                     const uint64_t v = read_field(b, q, f, w);
                     if (w.ftype[f] == FWA_FIELD_FLOAT) reinterpret_cast<uint32_t*>(o.col[j])[g] = (uint32_t)v;
                     else reinterpret_cast<uint64_t*>(o.col[j])[g] = v;
@@ -718,7 +754,8 @@ int grow_outputs(fwa_wire_decoder* d, int64_t n) {
     int rc;
     if ((rc = re((void**)&d->key, 8)) || (rc = re((void**)&d->ts, 8))) return rc;
     for (int j = 0; j < d->w.num_cols; ++j) {
-        if ((rc = re(&d->col[j], d->w.ftype[d->w.col_field[j]] == FWA_FIELD_FLOAT ? 4 : 8))) return rc;
+        const int ft = d->w.ftype[d->w.col_field[j]];
+        if ((rc = re(&d->col[j], ft == FWA_FIELD_FLOAT ? 4 : ft == FWA_FIELD_DECIMAL ? 16 : 8))) return rc;
         if (d->w.format == FWA_WIRE_ROWDATA && (rc = re((void**)&d->col_null[j], 1))) return rc;
     }
     if (d->w.format == FWA_WIRE_ROWDATA && (rc = re((void**)&d->key_null, 1))) return rc;
@@ -775,7 +812,13 @@ int fwa_wire_create(const fwa_wire_schema* s, fwa_wire_decoder** out) {
     w.nullbits = ((s->arity + 63 + 8) / 64) * 8;                  // BinaryRowData.calculateBitSetWidthInBytes
     for (int f = 0; f < s->arity; ++f) {
         const int t = s->field[f];
-        if (t < FWA_FIELD_LONG || t > FWA_FIELD_STRING) return bad(FWA_E_UNSUPPORTED, "unsupported field type");
+        if (t < FWA_FIELD_LONG || (t > FWA_FIELD_STRING && t != FWA_FIELD_DECIMAL)) return bad(FWA_E_UNSUPPORTED, "unsupported field type");
+        if (t == FWA_FIELD_DECIMAL) {
+            if (s->format != FWA_WIRE_ROWDATA)
+                return bad(FWA_E_UNSUPPORTED, "DECIMAL fields are decoded in ROWDATA rows only: a Tuple's BigDecSerializer is "
+                                              "another format");
+            ++w.ndecf;
+        }
         if (t == FWA_FIELD_STRING) {
             if (s->format != FWA_WIRE_ROWDATA)
                 return bad(FWA_E_UNSUPPORTED, "STRING fields are decoded in ROWDATA rows only: a Tuple's StringSerializer writes "
@@ -796,6 +839,7 @@ int fwa_wire_create(const fwa_wire_schema* s, fwa_wire_decoder** out) {
     for (int j = 0; j < s->num_cols; ++j) {
         if (s->col_field[j] < 0 || s->col_field[j] >= s->arity) return bad(FWA_E_ARG, "col_field out of range");
         if (w.ftype[s->col_field[j]] == FWA_FIELD_STRING) return bad(FWA_E_ARG, "a STRING field cannot be a value column");
+        if (w.ftype[s->col_field[j]] == FWA_FIELD_DECIMAL) ++w.ndec;
         w.col_field[j] = s->col_field[j];
     }
     int value_len;
@@ -811,7 +855,7 @@ int fwa_wire_create(const fwa_wire_schema* s, fwa_wire_decoder** out) {
     for (int t = 0; t < 6; ++t) mx = std::max(mx, w.body[t]);
     w.step = 4 + mx;
     if (w.step > kMaxStep) return bad(FWA_E_UNSUPPORTED, "elements longer than 249 bytes");
-    if (w.nstr > 0) w.step = kMaxStep;                            // records up to the ceiling; body[0..1] are the shortest
+    if (w.nstr + w.ndecf > 0) w.step = kMaxStep;                  // records up to the ceiling; body[0..1] are the shortest
     d->device = s->device;
     hipError_t e;
     if ((e = hipSetDevice(d->device)) != hipSuccess || (e = hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking)) != hipSuccess ||
@@ -916,7 +960,7 @@ int fwa_wire_decode(fwa_wire_decoder* d, const uint8_t* bytes, int64_t nbytes, i
     WCK(hipMemsetAsync(d->d_st, 0, sizeof(WireStatus), st));
     WCK(hipEventRecord(d->ev[0], st));
     const unsigned grid = (unsigned)std::min<int64_t>(nchunks, kPersistBlocks);
-    const bool var = w.nstr > 0;
+    const bool var = w.nstr + w.ndecf > 0;
     if (var) hipLaunchKernelGGL(wire_scan_kernel<true>, dim3(grid), dim3(64), 0, st, in, nbytes, nchunks, w, aligned, d->map0);
     else hipLaunchKernelGGL(wire_scan_kernel<false>, dim3(grid), dim3(64), 0, st, in, nbytes, nchunks, w, aligned, d->map0);
     WCK(hipGetLastError());
@@ -968,8 +1012,10 @@ int fwa_wire_decode(fwa_wire_decoder* d, const uint8_t* bytes, int64_t nbytes, i
         o.evt_tag = d->d_evt_tag;
         o.evt_val = d->d_evt_val;
         o.evt_cap = d->evt_cap;
-        if (var) hipLaunchKernelGGL(wire_decode_kernel<true>, dim3(grid), dim3(64), 0, st, in, nbytes, nchunks, w, aligned,
-                                    d->ent, d->rec, d->evt, o);
+        if (w.ndec > 0) hipLaunchKernelGGL((wire_decode_kernel<true, true>), dim3(grid), dim3(64), 0, st, in, nbytes, nchunks, w,
+                                           aligned, d->ent, d->rec, d->evt, o);
+        else if (var) hipLaunchKernelGGL(wire_decode_kernel<true>, dim3(grid), dim3(64), 0, st, in, nbytes, nchunks, w, aligned,
+                                         d->ent, d->rec, d->evt, o);
         else hipLaunchKernelGGL(wire_decode_kernel<false>, dim3(grid), dim3(64), 0, st, in, nbytes, nchunks, w, aligned,
                                 d->ent, d->rec, d->evt, o);
         WCK(hipGetLastError());
@@ -997,6 +1043,7 @@ int fwa_wire_decode(fwa_wire_decoder* d, const uint8_t* bytes, int64_t nbytes, i
             if (hs.error == FWA_E_CORRUPT && hs.err_tag < 256) snprintf(m, sizeof m, "Corrupt stream, found tag: %d (element at byte %lld)", hs.err_tag, (long long)hs.err_pos);
             else if (hs.error == FWA_E_ARG) snprintf(m, sizeof m, "NULL rowtime field in the row at byte %lld", (long long)hs.err_pos);
             else if (hs.err_tag == kErrSlot) snprintf(m, sizeof m, "Corrupt stream: a STRING slot points outside its row (record at byte %lld)", (long long)hs.err_pos);
+            else if (hs.err_tag == kErrDecSlot) snprintf(m, sizeof m, "Corrupt stream: a DECIMAL slot names bytes outside its row, none or more than 16 (record at byte %lld)", (long long)hs.err_pos);
             else if (hs.err_tag == kErrTooLong) snprintf(m, sizeof m, "element longer than the %d-byte limit at byte %lld", (int)kMaxBody, (long long)hs.err_pos);
             else if (hs.err_tag >= 256) snprintf(m, sizeof m, "RowKind %d at byte %lld: window aggregation consumes insert-only rows", hs.err_tag - 256, (long long)hs.err_pos);
             else snprintf(m, sizeof m, "row size differs from the schema's fixed-length row at byte %lld", (long long)hs.err_pos);

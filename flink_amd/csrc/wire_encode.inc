@@ -23,12 +23,19 @@
 //     stores, the values byte-parallel like wire_gather_kernel's -- consecutive lanes take consecutive source bytes and
 //     find their row by a binary search over the wave's 65 offsets.
 //
+//   schemas with DECIMAL fields (DEC) take the same three passes, instantiated a second time: a non-NULL DECIMAL result
+//     adds 16 bytes to its element (AbstractBinaryWriter.writeDecimal :164-196), and the row's lane writes them through
+//     the sink in both the staged and the direct path -- the minimal big-endian bytes of the 128-bit value (BigInteger.
+//     toByteArray: bitLength / 8 + 1 of them, from the count of leading sign bits), zeros up to 16, slot = cursor << 32 |
+//     length. A NULL result is setNullAt (RowDataSerializer.toBinaryRow :196-212): the bit, a zero slot, nothing reserved.
+//     Schemas without a DECIMAL field run the instantiations they ran.
+//
 // The trailing events (a handful) are laid out on the host and copied behind the rows on the encoder's stream.
 // HBM traffic: every column read once, every output byte written once; VAR adds 16 B per row of sizes / offsets.
 
 namespace {
 
-enum EncClass { kEncI64 = 0, kEncI32 = 1, kEncF64 = 2, kEncF32 = 3, kEncStr = 4 };
+enum EncClass { kEncI64 = 0, kEncI32 = 1, kEncF64 = 2, kEncF32 = 3, kEncStr = 4, kEncDec = 5 };
 constexpr int kEncTile = 12 * 1024;          // VAR: LDS bytes of a staged tile (per single-wave block)
 constexpr int64_t kEncBlocks = 256 * 16;     // persistent single-wave blocks
 
@@ -37,11 +44,13 @@ struct EncConst {
     int32_t efix;                            // element bytes, length prefix included, fixed part only
     int32_t hdr;                             // prefix + tag + [timestamp]: where the value starts (5 or 13)
     int32_t row_size, nullbits;              // ROWDATA: fixed part of the row, width of its null-bit set
-    int32_t nstr;
+    int32_t nstr;                            // STRING fields (> 0: elements vary in size)
     int32_t ftype[FWA_WIRE_MAX_FIELDS];      // wire type
     int32_t scls[FWA_WIRE_MAX_FIELDS];       // EncClass of the source column
     int32_t adj[FWA_WIRE_MAX_FIELDS];        // added to an int64 source (WIN_TIME: -1)
     int32_t foff[FWA_WIRE_MAX_FIELDS];       // offset of the field (TUPLE) / its slot (ROWDATA) in the element
+    int32_t ndec;                            // DECIMAL fields (> 0: elements vary in size too); last, so that the members
+                                             // above keep their places in the kernel argument
 };
 
 struct EncCols {
@@ -104,7 +113,8 @@ __device__ __forceinline__ uint64_t enc_str_bytes(const uint8_t* __restrict__ p,
 
 // Row g's element (esize: its bytes, prefix included). COPY: with the bytes of its STRING values, 8 at a time through
 // the sink; otherwise those are left to the caller's copy pass. n: the rows of the call (the columns' end).
-template <bool VAR, bool COPY, class Sink>
+// DEC: the schema has DECIMAL fields; their 16 reserved bytes always go through the sink.
+template <bool VAR, bool COPY, bool DEC, class Sink>
 __device__ __forceinline__ void enc_element(const EncConst& c, const EncCols& k, int64_t g, int64_t esize, const Sink& s,
                                             int64_t n = 0) {
     const uint32_t L = (uint32_t)(esize - 4);
@@ -146,6 +156,20 @@ __device__ __forceinline__ void enc_element(const EncConst& c, const EncCols& k,
                           (int)std::min<int64_t>(8, len - o));
             s.zero(row + cursor + len, (int)(r8 - len));
             cursor += r8;
+        } else if (DEC && c.ftype[f] == FWA_FIELD_DECIMAL) {
+            const uint64_t* __restrict__ v = reinterpret_cast<const uint64_t*>(k.col[f]) + 2 * g;   // low, high
+            const uint64_t lo = v[0], hi = v[1];
+            const uint64_t sx = (uint64_t)((int64_t)hi >> 63);     // BigInteger.bitLength: the bits below the sign bits
+            const uint64_t xh = hi ^ sx, xl = lo ^ sx;
+            const int bits = xh ? 128 - __builtin_clzll(xh) : xl ? 64 - __builtin_clzll(xl) : 0;
+            const int len = bits / 8 + 1;                          // toByteArray: 1..16 bytes
+            const int sh = 128 - 8 * len;                          // the value's top `len` bytes, zeros behind them
+            const uint64_t top = sh >= 64 ? lo << (sh - 64) : sh ? (hi << sh) | (lo >> (64 - sh)) : hi;
+            const uint64_t low = sh >= 64 ? 0 : lo << sh;
+            slot = ((uint64_t)cursor << 32) | (uint64_t)len;
+            s.put((int)(row + cursor), __builtin_bswap64(top), 8);
+            s.put((int)(row + cursor) + 8, __builtin_bswap64(low), 8);
+            cursor += 16;
         } else slot = enc_load(c, k, f, g);
         s.put(c.foff[f], slot, 8);
     }
@@ -168,7 +192,7 @@ __global__ __launch_bounds__(64) void wire_enc_fixed_kernel(EncConst c, EncCols 
         __syncthreads();                                          // the previous tile has been streamed out
         for (int i = lane; i < nz; i += 64) enc_buf[i] = z;
         __syncthreads();
-        if (lane < m) enc_element<false, false>(c, k, base + lane, c.efix, EncLdsSink{w, lane * c.efix});
+        if (lane < m) enc_element<false, false, false>(c, k, base + lane, c.efix, EncLdsSink{w, lane * c.efix});
         __syncthreads();
         uint8_t* dst = out + tile * (int64_t)full;                // 16-byte aligned (out is, full is a multiple of 16)
         const int nfull = bytes >> 4;
@@ -179,12 +203,17 @@ __global__ __launch_bounds__(64) void wire_enc_fixed_kernel(EncConst c, EncCols 
 }
 
 // ---- VAR: element sizes ----
+template <bool DEC>
 __global__ __launch_bounds__(256) void wire_enc_size_kernel(EncConst c, EncCols k, int64_t n, int64_t* __restrict__ size) {
     for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g <= n; g += (int64_t)gridDim.x * blockDim.x) {
         int64_t s = 0;
         if (g < n) {
             s = c.efix;
             for (int f = 0; f < c.arity; ++f) {
+                if (DEC && c.ftype[f] == FWA_FIELD_DECIMAL) {
+                    if (!(k.nul[f] && k.nul[f][g])) s += 16;
+                    continue;
+                }
                 if (c.ftype[f] != FWA_FIELD_STRING || (k.nul[f] && k.nul[f][g])) continue;
                 const int64_t len = std::max<int64_t>(0, (int64_t)k.soff[f][g + 1] - k.soff[f][g]);   // (offsets never decrease)
                 if (len > 7) s += (len + 7) & ~7ll;
@@ -195,6 +224,7 @@ __global__ __launch_bounds__(256) void wire_enc_size_kernel(EncConst c, EncCols 
 }
 
 // ---- VAR: the write pass ----
+template <bool DEC>
 __global__ __launch_bounds__(64) void wire_enc_var_kernel(EncConst c, EncCols k, int64_t n, const int64_t* __restrict__ eoff,
                                                            uint8_t* __restrict__ out) {
     __shared__ u32x4 buf[(kEncTile + 48) / 16];
@@ -223,13 +253,18 @@ __global__ __launch_bounds__(64) void wire_enc_var_kernel(EncConst c, EncCols k,
             const int nz = (int)((skew + tb + 15) >> 4) + 1;
             for (int i = lane; i < nz; i += 64) buf[i] = z;
             __syncthreads();
-            if (lane < m) enc_element<true, true>(c, k, g, esize, EncLdsSink{w, (int)epos}, n);
+            if (lane < m) enc_element<true, true, DEC>(c, k, g, esize, EncLdsSink{w, (int)epos}, n);
         } else {
             // a run longer than the LDS tile: everything but the values' bytes by the row's lane, then those bytes field by
-            // field (their variable-length parts follow in field order), byte-parallel over the wave
-            if (lane < m) enc_element<true, false>(c, k, g, esize, EncGlobalSink{out + es});
+            // field (their variable-length parts follow in field order, the 16 bytes of a DECIMAL, already written, among
+            // them), byte-parallel over the wave
+            if (lane < m) enc_element<true, false, DEC>(c, k, g, esize, EncGlobalSink{out + es});
             int64_t cursor = c.row_size;
             for (int f = 0; f < c.arity; ++f) {
+                if (DEC && c.ftype[f] == FWA_FIELD_DECIMAL) {
+                    if (lane < m && !(k.nul[f] && k.nul[f][g])) cursor += 16;
+                    continue;
+                }
                 if (c.ftype[f] != FWA_FIELD_STRING) continue;
                 __syncthreads();                                  // the last field's offsets have been read
                 if (lane < m) {
@@ -328,7 +363,7 @@ int egrow(fwa_wire_encoder* e, T** p, int64_t* cap, int64_t need, bool pinned = 
     return 0;
 }
 
-// Result column class of an aggregate kind (enum fwa_agg_kind); -1 unknown, -2 DECIMAL. *raw: FIRST_* / SEL_* bits.
+// Result column class of an aggregate kind (enum fwa_agg_kind); -1 unknown. *raw: FIRST_* / SEL_* bits.
 int agg_class(int kind, bool* raw) {
     *raw = false;
     switch (kind & ~FWA_AGG_DISTINCT) {
@@ -338,12 +373,12 @@ int agg_class(int kind, bool* raw) {
         case 18: case 19: case 20: case 25: case 26: return kEncI32;
         case 21: case 31: *raw = true; return kEncI64;
         case 22: case 32: *raw = true; return kEncI32;
-        case 14: case 15: case 16: case 17: return -2;
+        case 14: case 15: case 16: case 17: return kEncDec;       // 16 bytes per row: DECIMAL(38, s)
         default: return -1;
     }
 }
 
-int class_bytes(int cls) { return (cls == kEncI64 || cls == kEncF64) ? 8 : 4; }
+int class_bytes(int cls) { return cls == kEncDec ? 16 : (cls == kEncI64 || cls == kEncF64) ? 8 : 4; }
 
 int event_bytes(const fwa_wire_event& ev, uint8_t* p) {          // StreamElementSerializer.serialize :169-184
     auto be = [&](uint8_t* q, uint64_t v, int nb) { for (int b = 0; b < nb; ++b) q[b] = (uint8_t)(v >> (8 * (nb - 1 - b))); };
@@ -383,13 +418,16 @@ int fwa_wire_enc_create(const fwa_wire_out_schema* s, fwa_wire_encoder** out) {
     c.hdr = c.with_ts ? 13 : 5;
     c.nullbits = ((s->arity + 63 + 8) / 64) * 8;                  // BinaryRowData.calculateBitSetWidthInBytes
     c.row_size = c.nullbits + 8 * s->arity;
-    static const char* tname[] = {"LONG", "DOUBLE", "FLOAT", "INT", "STRING"};
-    static const char* cname[] = {"an int64", "an int32", "a double", "a float", "a STRING"};
+    static const char* tname[] = {"LONG", "DOUBLE", "FLOAT", "INT", "STRING", "?", "DECIMAL"};
+    static const char* cname[] = {"an int64", "an int32", "a double", "a float", "a STRING", "a DECIMAL"};
     int off = c.hdr;
     for (int f = 0; f < s->arity; ++f) {
         const int t = s->field[f];
         const std::string at = "field " + std::to_string(f) + ": ";
-        if (t < FWA_FIELD_LONG || t > FWA_FIELD_STRING) return bad(FWA_E_ARG, at + "unknown field type");
+        if (t < FWA_FIELD_LONG || (t > FWA_FIELD_STRING && t != FWA_FIELD_DECIMAL)) return bad(FWA_E_ARG, at + "unknown field type");
+        if (t == FWA_FIELD_DECIMAL && s->format != FWA_WIRE_ROWDATA)
+            return bad(FWA_E_ARG, at + "DECIMAL fields are written in ROWDATA rows only (a Tuple's BigDecSerializer is another "
+                                       "format)");
         if (t == FWA_FIELD_STRING && s->format != FWA_WIRE_ROWDATA)
             return bad(FWA_E_ARG, at + "STRING fields are written in ROWDATA rows only (a Tuple's StringSerializer writes "
                                        "varint-prefixed UTF-16 code units)");
@@ -410,9 +448,9 @@ int fwa_wire_enc_create(const fwa_wire_out_schema* s, fwa_wire_encoder** out) {
             case FWA_SRC_AGG:
                 if (s->src_index[f] < 0 || s->src_index[f] >= FWA_MAX_AGGS) return bad(FWA_E_ARG, at + "AGG index out of range");
                 cls = agg_class(s->src_kind[f], &raw);
-                if (cls == -2)
-                    return bad(FWA_E_UNSUPPORTED, at + "DECIMAL aggregate results are not encoded: the reference row carries a "
-                                                       "DecimalData, non-compact for the DECIMAL(38) sums");
+                if (cls == kEncDec && t != FWA_FIELD_DECIMAL)
+                    return bad(FWA_E_UNSUPPORTED, at + "a DECIMAL aggregate result is written as FWA_FIELD_DECIMAL only: the "
+                                                       "reference row carries a non-compact DecimalData, DECIMAL(38, s)");
                 if (cls < 0) return bad(FWA_E_ARG, at + "unknown aggregate kind");
                 break;
             default: return bad(FWA_E_ARG, at + "unknown source");
@@ -423,6 +461,7 @@ int fwa_wire_enc_create(const fwa_wire_out_schema* s, fwa_wire_encoder** out) {
             case kEncI32: ok = t == FWA_FIELD_INT || t == FWA_FIELD_LONG || (raw && t == FWA_FIELD_FLOAT); break;
             case kEncF64: ok = t == FWA_FIELD_DOUBLE; break;
             case kEncF32: ok = t == FWA_FIELD_FLOAT; break;
+            case kEncDec: ok = t == FWA_FIELD_DECIMAL; break;
             default: ok = t == FWA_FIELD_STRING; break;
         }
         if (!ok) return bad(FWA_E_ARG, at + cname[cls] + " source cannot be written as " + tname[t]);
@@ -430,6 +469,7 @@ int fwa_wire_enc_create(const fwa_wire_out_schema* s, fwa_wire_encoder** out) {
         c.scls[f] = cls;
         c.adj[f] = s->src[f] == FWA_SRC_WIN_TIME ? -1 : 0;
         if (t == FWA_FIELD_STRING) ++c.nstr;
+        if (t == FWA_FIELD_DECIMAL) ++c.ndec;
         if (s->format == FWA_WIRE_TUPLE) { c.foff[f] = off; off += field_bytes(t); }
         else c.foff[f] = c.hdr + 4 + c.nullbits + 8 * f;
     }
@@ -545,7 +585,8 @@ int fwa_wire_encode(fwa_wire_encoder* e, const fwa_out* rows, const fwa_wire_key
             at += (x.bytes + 15) & ~15ll;
         }
     }
-    const bool var = c.nstr > 0;
+    const bool var = c.nstr + c.ndec > 0;
+    const bool dec = c.ndec > 0;
     int64_t rows_bytes = n * c.efix;
     float ms_size = 0, ms_scan = 0, ms_write = 0;
     const unsigned grid = (unsigned)std::min<int64_t>((n + 63) / 64, kEncBlocks);
@@ -561,7 +602,9 @@ int fwa_wire_encode(fwa_wire_encoder* e, const fwa_out* rows, const fwa_wire_key
             e->row_cap = cap;
         }
         ECK(hipEventRecord(e->ev[0], st));
-        hipLaunchKernelGGL(wire_enc_size_kernel, dim3((unsigned)std::min<int64_t>((n + 256) / 256, 4096)), dim3(256), 0, st, c, k, n, e->d_size);
+        const dim3 sgrid((unsigned)std::min<int64_t>((n + 256) / 256, 4096));
+        if (dec) hipLaunchKernelGGL(wire_enc_size_kernel<true>, sgrid, dim3(256), 0, st, c, k, n, e->d_size);
+        else hipLaunchKernelGGL(wire_enc_size_kernel<false>, sgrid, dim3(256), 0, st, c, k, n, e->d_size);
         ECK(hipGetLastError());
         ECK(hipEventRecord(e->ev[1], st));
         size_t tb = 0;
@@ -585,7 +628,8 @@ int fwa_wire_encode(fwa_wire_encoder* e, const fwa_out* rows, const fwa_wire_key
     if (int rc = egrow(e, &e->d_out, &e->out_cap, nbytes + 16)) return rc;
     if (n > 0) {
         ECK(hipEventRecord(e->ev[3], st));
-        if (var) hipLaunchKernelGGL(wire_enc_var_kernel, dim3(grid), dim3(64), 0, st, c, k, n, e->d_off, e->d_out);
+        if (dec) hipLaunchKernelGGL(wire_enc_var_kernel<true>, dim3(grid), dim3(64), 0, st, c, k, n, e->d_off, e->d_out);
+        else if (var) hipLaunchKernelGGL(wire_enc_var_kernel<false>, dim3(grid), dim3(64), 0, st, c, k, n, e->d_off, e->d_out);
         else hipLaunchKernelGGL(wire_enc_fixed_kernel, dim3(grid), dim3(64), (size_t)(64 * c.efix + 32), st, c, k, n, e->d_out);
         ECK(hipGetLastError());
         ECK(hipEventRecord(e->ev[4], st));

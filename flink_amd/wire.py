@@ -15,6 +15,10 @@ STRING fields (CHAR / VARCHAR / STRING of ROWDATA rows) come back through `Decod
 (offsets, bytes, null) device views; `NetworkInput(schema, engine, keydict=kd, key_parts=[...])` turns them and the
 value columns into key dictionary ids per run of records, so a VARCHAR-keyed Table job runs from the channel's bytes.
 
+DECIMAL fields (precision > 18, non-compact, ROWDATA rows) decode to int64 [n, 2] (low, high) columns -- the layout
+`_abi.dec128_column` makes and SUM_DEC128 / AVG_DEC128 read -- and the DECIMAL aggregates' results are written as
+"DECIMAL" fields by the encoder. A DECIMAL with precision <= 18 is its unscaled long: "LONG" in both directions.
+
 The other direction: `WireEncoder` binds fwa_wire_encode -- the SoA columns of a watermark step (fwa_out, and the decoded
 key dictionary columns of a Table job) become the bytes RecordWriter would have produced, in HBM -- and `NetworkOutput`
 is the mirror of RecordWriterOutput (flink-streaming-java/.../runtime/io/RecordWriterOutput.java:131-135 and its
@@ -31,8 +35,8 @@ from .keydict import FIELD as KEY_FIELD, KeyStrings
 
 MAX_FIELDS = 16
 FORMATS = {"TUPLE": 0, "ROWDATA": 1}
-FIELDS = {"LONG": 0, "DOUBLE": 1, "FLOAT": 2, "INT": 3, "STRING": 4}
-FIELD_DTYPE = {0: "i8", 1: "f8", 2: "f4", 3: "i8"}           # value-column dtype per field type
+FIELDS = {"LONG": 0, "DOUBLE": 1, "FLOAT": 2, "INT": 3, "STRING": 4, "DECIMAL": 6}   # (5 is unassigned)
+FIELD_DTYPE = {0: "i8", 1: "f8", 2: "f4", 3: "i8", 6: "i8"}  # value-column dtype per field type (DECIMAL: two per record)
 TAG_REC_WITH_TIMESTAMP, TAG_REC_WITHOUT_TIMESTAMP, TAG_WATERMARK, TAG_LATENCY_MARKER, TAG_STREAM_STATUS, \
     TAG_RECORD_ATTRIBUTES = range(6)
 WIRE_DEVICE_BYTES = 0x1
@@ -61,7 +65,7 @@ class WireStats(C.Structure):
 
 
 def make_schema(fields, key_field, ts_field=-1, cols=(), fmt="TUPLE", device=0, max_bytes=0):
-    """fields: field type names in value order ("LONG", "DOUBLE", "FLOAT", "INT", and "STRING" in ROWDATA rows);
+    """fields: field type names in value order ("LONG", "DOUBLE", "FLOAT", "INT", and "STRING" / "DECIMAL" in ROWDATA rows);
     key_field -1 (schemas with a STRING field) = the caller builds the key; ts_field -1 = the StreamRecord
     timestamp; cols: the fields that become value columns 0, 1, ..."""
     s = Schema()
@@ -105,8 +109,13 @@ class DecodedBatch:
         n = self.n_records
         self.key = dev_view(b.key, n, np.dtype("i8")) if b.key else None
         self.ts = dev_view(b.ts, n, np.dtype("i8"))
-        self.cols = [dev_view(b.col[j], n, np.dtype(FIELD_DTYPE[schema.field[schema.col_field[j]]]))
-                     for j in range(schema.num_cols)]
+        self.cols = []
+        for j in range(schema.num_cols):
+            t = schema.field[schema.col_field[j]]
+            if t == FIELDS["DECIMAL"]:                             # 16-byte values as int64 [n, 2] (low, high)
+                self.cols.append(dev_view(b.col[j], 2 * n, np.dtype("i8")).view(n, 2))
+            else:
+                self.cols.append(dev_view(b.col[j], n, np.dtype(FIELD_DTYPE[t])))
         rowdata = schema.format == FORMATS["ROWDATA"]
         self.col_null = [dev_view(b.col_null[j], n, np.dtype("u1")) for j in range(schema.num_cols)] if rowdata else None
         self.key_null = dev_view(b.key_null, n, np.dtype("u1")) if rowdata and b.key_null else None
@@ -312,9 +321,10 @@ class EncStats(C.Structure):                # fwa_wire_enc_stats
 
 def make_out_schema(fields, fmt="TUPLE", record_ts=None, device=0, max_bytes=0):
     """fields, in the value's order: (wire type, source) pairs. The wire type is "LONG" / "DOUBLE" / "FLOAT" / "INT", or
-    "STRING" in ROWDATA rows; the source is "KEY", "WIN_START", "WIN_END", "WIN_TIME" (win_end - 1), ("AGG", j, kind) with
-    the aggregate's kind name as in flink_amd._abi.AGG_KINDS (it fixes the dtype of the result column), or
-    ("KEYCOL", k, type) with the key dictionary column's type ("BIGINT" / "INT" / "DOUBLE" / "STRING").
+    "STRING" / "DECIMAL" in ROWDATA rows; the source is "KEY", "WIN_START", "WIN_END", "WIN_TIME" (win_end - 1),
+    ("AGG", j, kind) with the aggregate's kind name as in flink_amd._abi.AGG_KINDS (it fixes the dtype of the result
+    column), or ("KEYCOL", k, type) with the key dictionary column's type ("BIGINT" / "INT" / "DOUBLE" / "STRING").
+    "DECIMAL" takes exactly the DECIMAL aggregates ("SUM_DEC" / "AVG_DEC" / "SUM_DEC128" / "AVG_DEC128": a DECIMAL(38, s)).
     record_ts: None (TAG_REC_WITHOUT_TIMESTAMP, Table rows) or "WIN_TIME" (the DataStream record timestamp win_end - 1).
     The pairing of sources and wire types is checked by fwa_wire_enc_create (WireEncoder)."""
     fields = list(fields)
@@ -333,6 +343,9 @@ def make_out_schema(fields, fmt="TUPLE", record_ts=None, device=0, max_bytes=0):
         if t not in FIELDS:
             raise ValueError("field %d: unknown wire type %r" % (i, t))
         s.field[i] = FIELDS[t]
+        if t == "DECIMAL" and not (isinstance(src, (tuple, list)) and len(src) == 3 and src[0] == "AGG" and src[2] in A.DEC_KINDS):
+            raise ValueError("field %d: wire type 'DECIMAL' takes a DECIMAL aggregate, ('AGG', j, kind) with kind in %s, not %r"
+                             % (i, "/".join(A.DEC_KINDS), src))
         if isinstance(src, str):
             if src not in SOURCES or src in ("AGG", "KEYCOL"):
                 raise ValueError("field %d: source %r (AGG and KEYCOL are (name, index, kind) triples)" % (i, src))

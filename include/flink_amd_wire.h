@@ -26,21 +26,36 @@
  * exactly as processElement would. Element boundaries are found on the GPU (every chunk parses all its
  * candidate entry offsets; the chunk maps are composed hierarchically), so no host pass touches the bytes.
  *
- * Supported value types: BIGINT / TIMESTAMP(p<=3) / TIMESTAMP_LTZ(p<=3) as FWA_FIELD_LONG, DOUBLE, FLOAT, INT, and
+ * Supported value types: BIGINT / TIMESTAMP(p<=3) / TIMESTAMP_LTZ(p<=3) / DECIMAL(p<=18) as FWA_FIELD_LONG (a compact
+ * DECIMAL is its unscaled long in the 8-byte slot, AbstractBinaryWriter.writeDecimal :164-171), DOUBLE, FLOAT, INT, and
  * in ROWDATA rows CHAR / VARCHAR / STRING as FWA_FIELD_STRING (BinaryRowData's layout, AbstractBinaryWriter.java:
  * 80-105,279-334: a value of at most 7 bytes sits in its slot, top bit set and the length in the top byte; a longer
  * one in the row's variable-length part, slot = offset << 32 | length; the decoder follows each slot's own top bit
  * and does not assume that short values are inline). The bytes are handed on as they are, UTF-8 is not interpreted.
  * STRING fields come back through fwa_wire_strings_of in the layout fwa_key_strings takes, so a VARCHAR-keyed Table
  * job feeds fwa_keydict_encode from the channel's bytes without a host pass.
+ * In ROWDATA rows a DECIMAL with precision > 18 is FWA_FIELD_DECIMAL (non-compact, AbstractBinaryWriter.writeDecimal
+ * :164-196, read back by BinarySegmentUtils.readDecimalData -> DecimalData.fromUnscaledBytes -> new BigInteger(bytes)):
+ * 16 bytes are reserved at the writer's cursor in the row's variable-length part and zeroed,
+ * DecimalData.toUnscaledBytes() (BigInteger.toByteArray: the minimal big-endian two's complement, bitLength / 8 + 1 =
+ * 1..16 bytes) is copied to their start, the slot is offset << 32 | length with the offset counted from the row's first
+ * byte, and the cursor advances by 16 whatever the length; the variable-length parts follow the fixed part in field
+ * order, interleaved with the 8-rounded parts of long STRING values. A NULL DECIMAL has two forms on the wire:
+ * RowDataSerializer.toBinaryRow (:196-212, the form the window operator's JoinedRowData output goes through) calls
+ * setNullAt -- the null bit, a zero slot, nothing reserved -- while a row built directly by a BinaryRowWriter may come
+ * from writeDecimal(pos, null, precision) -- the null bit, slot = cursor << 32 | 0, 16 zero bytes reserved. The decoder
+ * accepts both (it reads the null bit first and never interprets the slot of a NULL field); the encoder writes the
+ * first. A decoded DECIMAL column is 16-byte little-endian two's complement values, the input of FWA_SUM_DEC128 /
+ * FWA_AVG_DEC128; the 38-digit bound is theirs to apply, not the decoder's.
  *
  * Limits. An element (tag byte to its last byte; the 4-byte length prefix's value) may be at most 249 bytes: the
  * boundary maps keep entry offsets in a byte. A longer record ends the call with FWA_E_UNSUPPORTED and its byte
  * position, never FWA_E_CORRUPT; raising the ceiling needs 16-bit entry offsets in the maps and is a follow-up.
  * Not supported (FWA_E_UNSUPPORTED): STRING fields of TUPLE values (StringSerializer writes varint-prefixed UTF-16
  * code units, and DataStream String keys are FWA_KEY_PREHASHED), non-INSERT RowKinds, LZ4-compressed buffers
- * (taskmanager.network.compression), and the other variable-length SQL types (DECIMAL with p > 18, TIMESTAMP with
- * p > 3). Status codes: include/flink_amd.h.
+ * (taskmanager.network.compression), DECIMAL fields of TUPLE values (BigDecSerializer is another format) or as key
+ * dictionary columns, and the other variable-length SQL types (TIMESTAMP with p > 3). Status codes:
+ * include/flink_amd.h.
  */
 #ifndef FLINK_AMD_WIRE_H
 #define FLINK_AMD_WIRE_H
@@ -72,10 +87,16 @@ enum fwa_wire_format {
     FWA_WIRE_ROWDATA = 1   /* RowDataSerializer -> BinaryRowDataSerializer (Table runtime rows) */
 };
 
-/* Field types (java.lang.Long / BIGINT / compact TIMESTAMP, Double / DOUBLE, Float / FLOAT, Integer / INT, and
- * CHAR / VARCHAR / STRING of FWA_WIRE_ROWDATA rows). A STRING field cannot be key_field, ts_field or a col_field
- * (FWA_E_ARG); with FWA_WIRE_TUPLE it is FWA_E_UNSUPPORTED. */
-enum fwa_wire_field { FWA_FIELD_LONG = 0, FWA_FIELD_DOUBLE = 1, FWA_FIELD_FLOAT = 2, FWA_FIELD_INT = 3, FWA_FIELD_STRING = 4 };
+/* Field types (java.lang.Long / BIGINT / compact TIMESTAMP / compact DECIMAL, Double / DOUBLE, Float / FLOAT, Integer /
+ * INT, and in FWA_WIRE_ROWDATA rows CHAR / VARCHAR / STRING and DECIMAL(p > 18)). A STRING field cannot be key_field,
+ * ts_field or a col_field (FWA_E_ARG); with FWA_WIRE_TUPLE it is FWA_E_UNSUPPORTED. A DECIMAL field may be a col_field
+ * (or be read by no column: it is skipped); as key_field or ts_field it is FWA_E_ARG, with FWA_WIRE_TUPLE
+ * FWA_E_UNSUPPORTED. Value 5 is unassigned and stays refused (FWA_E_UNSUPPORTED by the decoder, FWA_E_ARG by the
+ * encoder), like every other unknown value. */
+enum fwa_wire_field {
+    FWA_FIELD_LONG = 0, FWA_FIELD_DOUBLE = 1, FWA_FIELD_FLOAT = 2, FWA_FIELD_INT = 3, FWA_FIELD_STRING = 4,
+    FWA_FIELD_DECIMAL = 6
+};
 
 typedef struct fwa_wire_schema {
     int32_t format;                          /* enum fwa_wire_format */
@@ -90,7 +111,9 @@ typedef struct fwa_wire_schema {
                                                 TumblingEventTimeWindows.java:83-86) */
     int32_t num_cols;                        /* value columns */
     int32_t col_field[FWA_MAX_COLS];         /* field -> value column c: LONG/INT -> int64, DOUBLE -> double,
-                                                FLOAT -> float (the input types fwa_push's aggregates read) */
+                                                FLOAT -> float (the input types fwa_push's aggregates read);
+                                                DECIMAL -> 16-byte little-endian two's complement (low 8 bytes, then
+                                                high), 16-byte aligned: the input of FWA_SUM_DEC128 / FWA_AVG_DEC128 */
     int32_t device;                          /* HIP device ordinal */
     int64_t max_bytes;                       /* sizing hint: largest nbytes per call (0 = 64 MiB; grows) */
 } fwa_wire_schema;
@@ -106,7 +129,7 @@ typedef struct fwa_wire_batch {
                                                 those bytes first in the next call */
     const int64_t* key;                      /* device [n_records] */
     const int64_t* ts;                       /* device [n_records] */
-    const void* col[FWA_MAX_COLS];           /* device [n_records] per value column */
+    const void* col[FWA_MAX_COLS];           /* device [n_records] per value column (a NULL DECIMAL field is 0) */
     const uint8_t* col_null[FWA_MAX_COLS];   /* ROWDATA: device [n_records], 1 = the field is NULL (the row's
                                                 null bit; fwa_push_nullable's null_cols); NULL for TUPLE */
     const uint8_t* key_null;                 /* ROWDATA: device [n_records], 1 = NULL key field */
@@ -129,7 +152,8 @@ const char* fwa_wire_last_error(const fwa_wire_decoder* d);
  * element boundary). Device bytes (FWA_WIRE_DEVICE_BYTES) must be complete when the call is made: the decoder
  * runs on its own stream (the caller synchronises the producer's stream first); everything is complete on
  * return. A malformed element (unknown tag, a length that does not match its tag and the schema, a row size int
- * that differs from the element's length, or a STRING slot pointing outside its row) returns
+ * that differs from the element's length, a STRING slot pointing outside its row, or the slot of a non-NULL DECIMAL
+ * column whose bytes lie outside the row's variable-length part or number 0 or more than 16) returns
  * FWA_E_CORRUPT ("Corrupt stream, found tag", StreamElementSerializer.java:208-210).
  * Device timing of the decode kernels accumulates in fwa_wire_stats. */
 int fwa_wire_decode(fwa_wire_decoder* d, const uint8_t* bytes, int64_t nbytes, int32_t flags,
@@ -176,7 +200,8 @@ int fwa_wire_strings_of(fwa_wire_decoder* d, int32_t field, fwa_wire_strings* ou
  *     BinaryRowWriter laid them out, AbstractBinaryWriter.java:80-105,279-334: RowKind in byte 0, the null bit of
  *     field i at bit i + 8, 8-byte little-endian slots, INT / FLOAT in the low half of a zeroed slot, setNullAt
  *     zeroing the slot, a STRING of at most 7 bytes in its slot with 0x80 | length in the top byte, a longer one in
- *     the variable-length part, zero-padded to 8 bytes, slot = offset << 32 | length).
+ *     the variable-length part, zero-padded to 8 bytes, slot = offset << 32 | length, a non-compact DECIMAL as laid
+ *     out at the top of this header: :164-196).
  * fwa_wire_encode replaces that loop for the rows of one watermark step: the SoA columns fwa_advance_watermark returns
  * (fwa_out), and for a dictionary-keyed Table job the key columns fwa_keydict_decode returns, become the bytes
  *   be32 L | tag | [be64 ts] | value          per row, in row order, followed by the non-record elements given
@@ -185,10 +210,14 @@ int fwa_wire_strings_of(fwa_wire_decoder* d, int32_t field, fwa_wire_strings* ou
  * caller; elements span buffers freely. The GPU decoder above is a receiver of these bytes.
  *
  * Limits. arity 1..FWA_WIRE_MAX_FIELDS; KEYCOL index < FWA_KEYDICT_MAX_ARITY; STRING fields in ROWDATA rows only
- * (FWA_E_ARG); a TUPLE value cannot carry NULLs (FWA_E_ARG at encode when a source has NULL flags); DECIMAL aggregates
- * are FWA_E_UNSUPPORTED (the reference row carries a DecimalData, non-compact for the DECIMAL(38) sums: the follow-up,
- * matching the decoder's own limit). The decoder's 249-byte element ceiling does not apply: element offsets are 64-bit,
- * and a STRING value may be as long as its int32 Arrow offsets allow. */
+ * (FWA_E_ARG); a TUPLE value cannot carry NULLs (FWA_E_ARG at encode when a source has NULL flags). The DECIMAL
+ * aggregates (FWA_SUM_DEC / FWA_AVG_DEC / FWA_SUM_DEC128 / FWA_AVG_DEC128: every result is a DECIMAL(38, s), 16 bytes
+ * per row in fwa_out) are written as FWA_FIELD_DECIMAL only, in ROWDATA rows: the minimal unscaled bytes in 16 reserved
+ * ones, a NULL result (agg_null) as setNullAt, the form RowDataSerializer.toBinaryRow :196-212 gives the operator's
+ * output rows. Under any other wire type they are FWA_E_UNSUPPORTED, and a FWA_FIELD_DECIMAL field takes no other
+ * source (FWA_E_ARG); a BigDecimal field of a TUPLE value (BigDecSerializer) is not written (FWA_E_ARG). Not supported:
+ * TIMESTAMP with p > 3. The decoder's 249-byte element ceiling does not apply: element offsets are 64-bit, and a STRING
+ * value may be as long as its int32 Arrow offsets allow. */
 
 /* Where a field's value comes from. */
 enum fwa_wire_src {
@@ -209,8 +238,9 @@ enum fwa_wire_record_ts {
  * window properties as the query does.
  * Allowed source -> wire type pairs (anything else is FWA_E_ARG at create): an int64 column -> LONG, or INT (the low
  * 32 bits, Java's narrowing cast); an int32 column -> INT, or LONG (sign-extended); double -> DOUBLE; float -> FLOAT;
- * a key dictionary STRING column -> STRING. FWA_FIRST_64 / FWA_SEL_64 hold a field's raw bits and also go out as
- * DOUBLE, FWA_FIRST_32 / FWA_SEL_32 also as FLOAT. */
+ * a key dictionary STRING column -> STRING; a DECIMAL aggregate (FWA_SRC_AGG with src_kind FWA_SUM_DEC .. FWA_AVG_DEC128,
+ * 14..17) -> DECIMAL and nothing else. FWA_FIRST_64 / FWA_SEL_64 hold a field's raw bits and also go out as DOUBLE,
+ * FWA_FIRST_32 / FWA_SEL_32 also as FLOAT. */
 typedef struct fwa_wire_out_schema {
     int32_t format;                          /* enum fwa_wire_format */
     int32_t arity;                           /* fields per value, 1..FWA_WIRE_MAX_FIELDS */
@@ -221,7 +251,8 @@ typedef struct fwa_wire_out_schema {
     int32_t src_kind[FWA_WIRE_MAX_FIELDS];   /* the result dtype of a column is not visible in fwa_out, so the schema
                                                 names it. FWA_SRC_AGG: the aggregate's fwa_agg_spec.kind (FWA_AGG_DISTINCT
                                                 bit allowed), which fixes its result column: [i64], [i32], [f64] or
-                                                [f32] as listed at enum fwa_agg_kind. FWA_SRC_KEYCOL: the column's enum
+                                                [f32] as listed at enum fwa_agg_kind, or the 16-byte DECIMAL results.
+                                                FWA_SRC_KEYCOL: the column's enum
                                                 fwa_key_field_type. Ignored otherwise */
     int32_t record_ts;                       /* enum fwa_wire_record_ts */
     int32_t device;                          /* HIP device ordinal */
@@ -258,8 +289,9 @@ typedef struct fwa_wire_bytes {
 
 typedef struct fwa_wire_encoder fwa_wire_encoder;
 
-/* FWA_E_ARG: unknown format / field / source, arity or an index out of range, STRING in a TUPLE value, a source ->
- * wire type pair that is not allowed. FWA_E_UNSUPPORTED: a DECIMAL aggregate source. FWA_E_DEVICE / FWA_E_OOM: HIP.
+/* FWA_E_ARG: unknown format / field / source, arity or an index out of range, STRING or DECIMAL in a TUPLE value, a
+ * source -> wire type pair that is not allowed. FWA_E_UNSUPPORTED: a DECIMAL aggregate source under a wire type other
+ * than FWA_FIELD_DECIMAL. FWA_E_DEVICE / FWA_E_OOM: HIP.
  * fwa_wire_enc_last_error(NULL) says why a create failed (per thread). */
 int fwa_wire_enc_create(const fwa_wire_out_schema* schema, fwa_wire_encoder** out);
 void fwa_wire_enc_destroy(fwa_wire_encoder* e);
@@ -282,8 +314,8 @@ typedef struct fwa_wire_enc_stats {
     int64_t rows_in;
     int64_t bytes_out;
     double encode_ms;                        /* HIP-event device time of the encode kernels (size + scan + write) */
-    double scan_ms;                          /* of which: the exclusive scan to element offsets (STRING schemas) */
-    double size_ms;                          /* of which: the size pass (STRING schemas) */
+    double scan_ms;                          /* of which: the exclusive scan to element offsets (STRING / DECIMAL schemas) */
+    double size_ms;                          /* of which: the size pass (STRING / DECIMAL schemas) */
 } fwa_wire_enc_stats;
 
 int fwa_wire_enc_get_stats(fwa_wire_encoder* e, fwa_wire_enc_stats* out);
