@@ -3577,6 +3577,7 @@ static int push_v2(fwa_engine* e, IngestArgs& a, bool* ran) {
     const bool narrow2 = e->opt_narrow != 0 && (e->opt_narrow == 1 || e->narrow) && layout == 0 && e->nv == 2 && vw == 1 &&
                          kgm == 0 && !pre && !a.pcount;
     e->narrow_used = narrow || narrow2;
+    const bool roll = !(e->opt_variant & 1024);
 #define P3LAUNCH(NV, IT, VW) do { \
         if (kgm == 0) partition3_kernel<NV, IT, 1024, VW, 0><<<grid, 1024, 0, e->stream>>>(pa, e->d_ec); \
         else if (kgm == 1) partition3_kernel<NV, IT, 1024, VW, 1><<<grid, 1024, 0, e->stream>>>(pa, e->d_ec); \
@@ -3588,6 +3589,9 @@ static int push_v2(fwa_engine* e, IngestArgs& a, bool* ran) {
         else partition3_kernel<NV, 4, 1024, 3, 2, 1><<<gp, 1024, 0, e->stream>>>(pa, e->d_ec); } while (0)
     if (pre) { if (e->nv == 0) PRELAUNCH(0); else PRELAUNCH(1); }
     else if (e->nv == 0) P3LAUNCH(0, 8, 3);
+    // rolling issue of the next tile's loads (partition3 ROLL); FWA_OPT_INGEST_VARIANT bit 10: in one burst behind the
+    // scan instead (A/B)
+    else if (narrow && roll) partition3_kernel<1, 6, 1024, 3, 0, 0, 1, 1, 1><<<grid, 1024, 0, e->stream>>>(pa, e->d_ec);
     else if (narrow) partition3_kernel<1, 6, 1024, 3, 0, 0, 1, 1><<<grid, 1024, 0, e->stream>>>(pa, e->d_ec);
     else if (narrow2) partition3_kernel<2, 4, 1024, 1, 0, 0, 0, 2><<<grid, 1024, 0, e->stream>>>(pa, e->d_ec);
     else if (e->nv == 1 && w16 && (vw & 1)) partition3_kernel<1, 6, 1024, 3, 0, 0, 1><<<grid, 1024, 0, e->stream>>>(pa, e->d_ec);

@@ -523,8 +523,14 @@ __device__ __forceinline__ void pre_apply_global(unsigned long long* table, uint
 // value's bits share one u64, the 8-byte value keeps its own (18 instead of 26 bytes per entry).
 // NW: narrow bucket entries -- key and BIGINT value as two sign-extended 32-bit halves of one u64 (10 instead of 18
 // bytes per entry with the u16 slice); a record whose key or value needs 64 bits takes the v1 replay.
-template <int NV, int ITEMS, int THREADS, int VW, int KG, int PRE = 0, int W16 = 0, int NW = 0>
+// ROLL (W16, not PRE; DESIGN.md section 5 "Rolling tile loads"): the next tile's loads are issued pair by pair from
+// inside the classify loop, each as soon as the registers of its pair are dead, instead of in one burst behind the
+// scan; the wait is per pair too, ahead of the pair's classify. No register set, tile or LDS more: only where the
+// loads are issued moves. The cold branches of classify (NULL flags, late-index list, spill list, the time-zone table
+// on the 64-bit division's branch) wait vmcnt(0) as before and then drain the loads in flight as well.
+template <int NV, int ITEMS, int THREADS, int VW, int KG, int PRE = 0, int W16 = 0, int NW = 0, int ROLL = 0>
 __global__ void __launch_bounds__(THREADS, 1) partition3_kernel(PartArgs a, const EngineConst* __restrict__ cp) {
+    static_assert(!ROLL || (W16 && !PRE), "rolling issue: paired loads; PRE reads the load registers behind a barrier");
     static_assert(THREADS == kMaxPart && ITEMS <= 8, "one partition cursor per thread; trash area of 8 x kMaxPart");
     static_assert(!PRE || NV <= 1, "pre-aggregation: COUNT [+ one BIGINT sum]");
     static_assert(!W16 || (ITEMS % 2 == 0 && KG != 2 && NV <= 1), "paired loads: even ITEMS, no key-hash column");
@@ -573,27 +579,30 @@ __global__ void __launch_bounds__(THREADS, 1) partition3_kernel(PartArgs a, cons
     // every load of a tile is issued before any is used; uniform branches sit outside the item loops
     // (a per-item select between a 4- and an 8-byte load made hipcc wait vmcnt(0) at every join)
     auto xof = [&](int j) -> int { return W16 ? 2 * ((j >> 1) * THREADS + tid) + (j & 1) : j * THREADS + tid; };
-    auto load = [&](Regs& R, int64_t t) {
-        if constexpr (W16) {   // pair p = records 2p, 2p+1 of the tile; a pair reaching past n is not loaded (its
-#pragma unroll                 // record n-1, if any, goes to the slow path below)
-            for (int jj = 0; jj < ITEMS / 2; ++jj) {
-                const int64_t pi = t * (kTile / 2) + (int64_t)jj * THREADS + tid;
-                const int64_t ip = 2 * pi + 1 < n ? pi : 0;
-                const ulonglong2 kk = reinterpret_cast<const ulonglong2*>(pkeys)[ip];
-                const longlong2 tt = reinterpret_cast<const longlong2*>(pts)[ip];
-                R.key[2 * jj] = kk.x; R.key[2 * jj + 1] = kk.y;
-                R.ts[2 * jj] = tt.x; R.ts[2 * jj + 1] = tt.y;
-                if constexpr (NV > 0) {
-                    if constexpr (w0) {
-                        const ulonglong2 vv = reinterpret_cast<const ulonglong2*>(pc0)[ip];
-                        R.v0[2 * jj] = vv.x; R.v0[2 * jj + 1] = vv.y;
-                    } else {
-                        const uint2 vv = reinterpret_cast<const uint2*>(pc0)[ip];
-                        R.v0[2 * jj] = vv.x; R.v0[2 * jj + 1] = vv.y;
-                    }
-                }
-                R.kh[2 * jj] = 0; R.kh[2 * jj + 1] = 0;
+    // W16: pair jj of tile t into items 2jj, 2jj+1 of R. Pair p = records 2p, 2p+1 of the tile; a pair reaching past n
+    // is not loaded (its record n-1, if any, goes to the slow path below).
+    auto load_pair = [&](Regs& R, int64_t t, int jj) {
+        const int64_t pi = t * (kTile / 2) + (int64_t)jj * THREADS + tid;
+        const int64_t ip = 2 * pi + 1 < n ? pi : 0;
+        const ulonglong2 kk = reinterpret_cast<const ulonglong2*>(pkeys)[ip];
+        const longlong2 tt = reinterpret_cast<const longlong2*>(pts)[ip];
+        R.key[2 * jj] = kk.x; R.key[2 * jj + 1] = kk.y;
+        R.ts[2 * jj] = tt.x; R.ts[2 * jj + 1] = tt.y;
+        if constexpr (NV > 0) {
+            if constexpr (w0) {
+                const ulonglong2 vv = reinterpret_cast<const ulonglong2*>(pc0)[ip];
+                R.v0[2 * jj] = vv.x; R.v0[2 * jj + 1] = vv.y;
+            } else {
+                const uint2 vv = reinterpret_cast<const uint2*>(pc0)[ip];
+                R.v0[2 * jj] = vv.x; R.v0[2 * jj + 1] = vv.y;
             }
+        }
+        R.kh[2 * jj] = 0; R.kh[2 * jj + 1] = 0;
+    };
+    auto load = [&](Regs& R, int64_t t) {
+        if constexpr (W16) {
+#pragma unroll
+            for (int jj = 0; jj < ITEMS / 2; ++jj) load_pair(R, t, jj);
             return;
         }
         int64_t ic[ITEMS];
@@ -635,6 +644,10 @@ __global__ void __launch_bounds__(THREADS, 1) partition3_kernel(PartArgs a, cons
     };
     long long pt = clock64();
     long long pacc[6] = {0, 0, 0, 0, 0, 0};
+    // phases: 0 classify (ROLL: with the waits per pair and the issue of the next tile's first pairs), 1 barrier
+    // behind classify, reservation (ROLL: and the issue of the last pair) and scan (not ROLL: and the issue of the
+    // next tile), 2 LDS scatter and the wait for the reservation, 3 stores, 4 barrier at the end of the tile, 5 the
+    // wait for the whole tile at the top (ROLL: empty)
 #define QMARK(k) do { if (KPROF(a.prof)) { const long long _t = clock64(); pacc[k] += _t - pt; pt = _t; } } while (0)
     Regs ra;
     const int64_t G = gridDim.x;
@@ -663,16 +676,28 @@ __global__ void __launch_bounds__(THREADS, 1) partition3_kernel(PartArgs a, cons
         // wait for the whole tile HERE, on every path: a loaded register consumed only on some paths (the
         // value, staged for accepted records only) stays "pending" in hipcc's waitcnt analysis, and the
         // next reuse of that register then waited vmcnt(0) -- draining the stores and the prefetch
+        // ROLL: the wait is per pair, just ahead of the pair's own classify (below) -- the later pairs of the tile
+        // are still landing while the first is classified
+        if constexpr (!ROLL) {
 #pragma unroll
-        for (int j = 0; j < ITEMS; ++j) {
-            consume(R.key[j]);
-            consume(R.ts[j]);
-            if constexpr (NV > 0) consume(R.v0[j]);
-            if constexpr (NV > 1) consume(R.v1[j]);
-            if constexpr (KG == 2) consume(R.kh[j]);
+            for (int j = 0; j < ITEMS; ++j) {
+                consume(R.key[j]);
+                consume(R.ts[j]);
+                if constexpr (NV > 0) consume(R.v0[j]);
+                if constexpr (NV > 1) consume(R.v1[j]);
+                if constexpr (KG == 2) consume(R.kh[j]);
+            }
         }
+        const int64_t nxt = nx < ntiles ? nx : tile;    // a block's last tile reloads itself (fixed count of loads)
 #pragma unroll
         for (int j = 0; j < ITEMS; ++j) {
+            if constexpr (ROLL != 0) {
+                if ((j & 1) == 0) {                     // every register of the pair, on every path (as above)
+                    consume(R.key[j]); consume(R.key[j + 1]);
+                    consume(R.ts[j]); consume(R.ts[j + 1]);
+                    if constexpr (NV > 0) { consume(R.v0[j]); consume(R.v0[j + 1]); }
+                }
+            }
             const int64_t i = t0 + xof(j);
             const int64_t key = (int64_t)R.key[j];
             const int64_t ts = R.ts[j];
@@ -745,6 +770,12 @@ __global__ void __launch_bounds__(THREADS, 1) partition3_kernel(PartArgs a, cons
                 }
                 else r_pos[j] = (p << 16) | atomicAdd(&hist[p], 1u);
             }
+            // ROLL: the pair's registers had their last use in the staging stores and the hist atomic above; tile nxt's
+            // loads of the same pair go out here, in flight through the rest of classify, the barrier, the scan and
+            // the scatter (the tile's last pair: behind the reservation, below)
+            if constexpr (ROLL != 0) {
+                if ((j & 1) != 0 && j != ITEMS - 1) load_pair(R, nxt, j >> 1);
+            }
         }
         if constexpr (PRE) {
             __syncthreads();                        // the tile's staged (key, rel) visible to every lane
@@ -781,6 +812,11 @@ __global__ void __launch_bounds__(THREADS, 1) partition3_kernel(PartArgs a, cons
         const uint32_t h = p < a.np ? hist[p] : 0u;
         const uint32_t g = h ? atomicAdd(&a.b_cnt[p * kSub + sub], h) : 0u;
         if (p < a.np) hist[p] = 0;                      // nobody else reads it again this tile: ready for the next one
+        // ROLL: the tile's last pair goes out behind the reservation, in every wave: the wait for g (at gbase, behind
+        // the LDS scatter) is then vmcnt(3) and leaves those three loads in flight; issued ahead of the reservation
+        // they would have to land first (vmcnt retires in order). Unconditional: under `wave owns a partition` hipcc's
+        // waitcnt analysis merged the paths and waited vmcnt(0) right behind the reservation.
+        if constexpr (ROLL != 0) load_pair(R, nxt, ITEMS / 2 - 1);
         // exclusive scan of the counts over p = tid: wave scan, per-wave sums, each thread adds the sums of the waves
         // before its own (one barrier; the partition p's run starts at toff[p] in the tile's staging order)
         {
@@ -798,7 +834,7 @@ __global__ void __launch_bounds__(THREADS, 1) partition3_kernel(PartArgs a, cons
             if (p < a.np) toff[p] = woff + incl - h;
             if (tid == THREADS - 1) s_total = woff + incl;
         }
-        load(R, nx < ntiles ? nx : tile);               // the next tile in flight from here on (unconditional)
+        if constexpr (ROLL == 0) load(R, nxt);          // the next tile in flight from here on (unconditional)
         if constexpr (PRE) for (int i = tid; i < kHt / 4; i += THREADS) ((uint4*)ht)[i] = make_uint4(0u, 0u, 0u, 0u);
         __syncthreads();                                // toff and s_total complete
         QMARK(1);

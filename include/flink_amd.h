@@ -631,7 +631,9 @@ enum fwa_option {
                                     instead of the one-pass fire that retires its slots itself, and every push uploads
                                     its slice tables instead of passing narrow ones in the kernel arguments; bit 9
                                     (512): the one-pass tumbling fire stores the identities over the slots it retires
-                                    instead of leaving them stale for the next two-phase push to overwrite */
+                                    instead of leaving them stale for the next two-phase push to overwrite; bit 10
+                                    (1024): Phase P of narrow COUNT + BIGINT SUM entries issues the next tile's loads in
+                                    one burst behind the scan instead of pair by pair from inside the classify loop */
     FWA_OPT_SLIDE_CARRIED = 13,  /* read only: sliding fires whose first window reused the previous run's carried
                                     window sums (fwa_get_option; set: 0 disables the reuse, 1 enables it, default) */
     FWA_OPT_FIRE_PARTIALS = 14,  /* read only: fwa_fire_partials calls that merged and fired on chip (fwa_get_option;

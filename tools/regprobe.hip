@@ -67,6 +67,7 @@ const void* regprobe_kernels[] = {
     (const void*)&partition3_kernel<1,6,1024,3,0,0,0,0>,
     (const void*)&partition3_kernel<1,6,1024,3,0,0,1,0>,
     (const void*)&partition3_kernel<1,6,1024,3,0,0,1,1>,
+    (const void*)&partition3_kernel<1,6,1024,3,0,0,1,1,1>,
     (const void*)&partition3_kernel<1,6,1024,3,1,0,0,0>,
     (const void*)&partition3_kernel<1,6,1024,3,2,0,0,0>,
     (const void*)&partition3_kernel<2,4,1024,0,0,0,0,0>,
