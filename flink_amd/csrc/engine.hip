@@ -42,6 +42,7 @@
 namespace {
 
 #include "ingest.inc"
+#include "ingest_launch.inc"
 
 
 // ------------------------------------------------------------------------------------------------
@@ -795,1151 +796,7 @@ __global__ void __launch_bounds__(TB) fire_slide_kernel(FireSlideArgs f, const E
     }
 }
 
-// ------------------------------------------------------------------------------------------------
-// sessions (merging windows): DataStream EventTimeSessionWindows + EventTimeTrigger (allowed lateness
-// L >= 0) and the Table legacy GROUP BY SESSION (TR/operators/window/WindowOperator.java:331-398 with
-// MergingWindowProcessFunction and EventTimeTriggers.afterEndOfWindow).
-//
-// State: a flat list of in-flight sessions {kid, start, end, acc[nacc]} (column 0 = COUNT), in no
-// particular order; no per-key cap. A push rebuilds it (DESIGN.md §2 "Sessions"):
-//  * Order-free records -- the lone window [ts, ts+gap) ends after the watermark (ts + gap - 1 > wm).
-//    Such a record is never dropped, never fires on arrival, and merging is a union of intersecting
-//    intervals, so the key's session set after the push is the connected components of (its in-flight
-//    sessions + its new windows) regardless of arrival order (MergingWindowSet.addWindow :153-236,
-//    TimeWindow.intersects/cover :116-124 -- touching windows merge). Bulk path: one radix sort by
-//    (kid, start), a segmented max-scan of the ends (a new session starts where start > every earlier
-//    end of the key), a cluster-id scan, and a wave-segmented reduction of the accumulators.
-//  * A key with at least one order-sensitive record in the push (lone window already ends at or before
-//    the watermark: it may be dropped, may fire on arrival with the session contents, or may be saved by
-//    a session an earlier record of the push created) goes through an arrival-order walk instead: its
-//    sessions and records sorted by (kid, arrival), one lane per key applying addWindow / isWindowLate /
-//    EventTimeTrigger.onElement in order (WindowOperator.java:288-389). Late firings are written to the
-//    late-row buffer (returned at the head of the next fwa_advance_watermark).
-//  * Fire at a watermark advance prev -> wm: every session with prev < end - 1 <= wm emits a row
-//    (EventTimeTrigger.onEventTime: sessions whose maxTimestamp <= prev already fired -- at a timer or
-//    on an element); every session with cleanup = end - 1 + L <= wm is cleared (clearAllState).
-
-struct SessCtr {                 // per-push device counters (zeroed by the host before a push / fire)
-    unsigned long long ts_min, ts_max;   // ord-encoded, over records and in-flight session starts (cell pre-aggregation:
-                                         // the smallest / largest cell number of the push)
-    unsigned long long n_special;        // records whose lone window ends at or before the watermark
-    unsigned long long n_bulk, n_sp;     // elements routed to the bulk / the arrival-order path
-    unsigned long long n_out_sp;         // sessions written by the arrival-order path
-    unsigned long long n_keep;           // fire: sessions kept
-    unsigned long long n_redo;           // cell path: elements outside the cell range (the push is redone)
-};
-
-struct SessList {                // one in-flight session list (SoA)
-    uint32_t* kid;
-    int64_t* start;
-    int64_t* end;
-    unsigned long long* acc;     // [nacc][stride]
-    int64_t stride;
-};
-
-struct Sess2Args {
-    const int64_t* keys;
-    const int64_t* ts;
-    const void* cols[FWA_MAX_COLS];
-    const int32_t* key_hash;
-    const int64_t* gapc;         // per-record gaps (DynamicEventTimeSessionWindows) or nullptr: fixed `gap`
-    const uint8_t* nulls[FWA_MAX_COLS];   // SQL NULL flags per value column (nullptr: no NULLs)
-    int64_t n;
-    int64_t wm, gap, lateness;
-    unsigned long long* key_table;
-    uint64_t key_mask;
-    int32_t seg_log, part_bits;
-    int64_t capacity;            // key-table capacity (side slot at capacity)
-    uint32_t* rkid;              // [n] kid per record (0xffffffff: rejected)
-    uint8_t* kflag;              // [capacity + 1] key has an order-sensitive record in this push
-    SessList in;                 // in-flight sessions before the push
-    int64_t n_in;
-    SessList out;                // after the push
-    // bulk path
-    int64_t base;                // smallest start of the push (records and in-flight sessions)
-    int32_t tb;                  // bits of (start - base) in the sort key (kid << tb | start - base)
-    int32_t all_sp;              // 1: route everything through the arrival-order path
-    unsigned long long* bkey;    // [nb] sort keys (then sorted)
-    uint32_t* bval;              // [nb] payload: bulk position, | 0x80000000 when its end is in pe (sessions,
-                                 // dynamic gaps)
-    unsigned long long* pk;      // [nb][pkw] the element's COUNT + accumulator words, in bulk order (one row per
-                                 // element gathered once after the sort, not one value column per accumulator)
-    int64_t* pe;                 // [nb] end of a flagged element
-    uint32_t* sg_kid;            // segment kernel staging: wave w's clusters at [h0(w), h0(w) + count(w)) (no atomics)
-    int64_t* sg_start;
-    int64_t* sg_end;
-    unsigned long long* sg_acc;  // [nacc][cap]
-    int64_t sg_cap;
-    uint32_t* sg_cnt;            // [nw + 1] clusters per wave
-    uint32_t* sg_off;            // [nw + 1] their exclusive sum
-    int64_t* sg_h0;              // [nw] first owned position per wave
-    int32_t pkw;
-    jm::UDiv64 gap_div;          // cell path: cell = (start - base) / gap, base = ctr->ts_min
-    int32_t seg_out;             // bulk sessions appended on ctr->n_out_sp by sess2_segment_kernel (the arrival-order
-                                 // path appends after them on the same counter)
-    int64_t* bend;               // [nb] window / session end per sorted element
-    int64_t* bmax;               // [nb] inclusive max of bend over the key so far (segmented scan)
-    uint32_t* bcid;              // [nb] head flags, then 1-based cluster ids (inclusive sum)
-    int64_t nb;
-    int32_t col_owner[1 + kMaxAggsInt];    // aggregate that feeds accumulator column c (-1: COUNT)
-    // arrival-order path
-    unsigned long long* skey;    // [ns] (kid << 32) | (0 for a session, 1 + record index)
-    uint32_t* sval;
-    int64_t nsp;
-    int64_t* sc_start;           // [ns] scratch session lists, one region per key run
-    int64_t* sc_end;
-    unsigned long long* sc_acc;  // [nacc][ns]
-    // late-firing rows
-    int64_t* lr_key;
-    int64_t* lr_start;
-    int64_t* lr_end;
-    void* lr_agg[FWA_MAX_AGGS];
-    unsigned long long* lr_n;
-    int64_t lr_cap;
-    SessCtr* ctr;
-    int32_t* dropidx;            // FWA_CFG_LATE_INDICES list (nullptr: not collected)
-    DevStatus* st;
-};
-
-__device__ __forceinline__ int64_t sess_cleanup(int64_t max_ts, int64_t lateness) {   // WindowOperator.cleanupTime :647-654
-    const int64_t ct = jm::wadd(max_ts, lateness);
-    return ct >= max_ts ? ct : LONG_MAX_J;
-}
-
-__device__ __forceinline__ void wave_minmax(unsigned long long lo, unsigned long long hi, unsigned long long* dlo,
-                                            unsigned long long* dhi) {
-    for (int sh = 32; sh >= 1; sh >>= 1) {
-        const unsigned long long a = __shfl_xor(lo, sh), b = __shfl_xor(hi, sh);
-        lo = a < lo ? a : lo;
-        hi = b > hi ? b : hi;
-    }
-    if ((threadIdx.x & 63) == 0 && lo <= hi) { atomicMin(dlo, lo); atomicMax(dhi, hi); }
-}
-
-// Pass 1 over the records: key-group check, kid, order-sensitivity flag per key, start range.
-__global__ void __launch_bounds__(kBlock) sess2_classify_kernel(Sess2Args a, const EngineConst* __restrict__ cp) {
-    const EngineConst& c = *cp;
-    unsigned long long lo = ~0ull, hi = 0ull, nsp = 0;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t key = a.keys[i];
-        const int64_t ts = a.ts[i];
-        a.rkid[i] = 0xffffffffu;
-        const int32_t kg = jm::key_group_of(key, c.key_kind, a.key_hash ? a.key_hash[i] : 0, c.max_par);
-        if (kg < c.kg_lo || kg > c.kg_hi) { raise_error(a.st, FWA_E_KEYGROUP); continue; }   // StateTable :300-307
-        const int64_t gap = a.gapc ? a.gapc[i] : a.gap;
-        if (gap <= 0) { raise_error(a.st, FWA_E_ARG); continue; }   // DynamicEventTimeSessionWindows.java:60-64
-        const int64_t kid = key_slot(a.key_table, a.key_mask, a.seg_log, a.part_bits, key, a.st);
-        if (kid < 0) { a.st->key_full = 1; raise_error(a.st, FWA_E_OOM); continue; }
-        a.rkid[i] = (uint32_t)kid;
-        if (jm::wsub(jm::wadd(ts, gap), 1) <= a.wm) { a.kflag[kid] = 1; ++nsp; }   // lone window maxTs <= wm
-        const unsigned long long o = jm::ord_i64(ts);
-        lo = o < lo ? o : lo;
-        hi = o > hi ? o : hi;
-    }
-    wave_minmax(lo, hi, &a.ctr->ts_min, &a.ctr->ts_max);
-    for (int sh = 32; sh >= 1; sh >>= 1) nsp += __shfl_xor(nsp, sh);
-    if ((threadIdx.x & 63) == 0 && nsp) atomicAdd(&a.ctr->n_special, nsp);
-}
-
-__global__ void __launch_bounds__(kBlock) sess2_range_kernel(Sess2Args a) {
-    unsigned long long lo = ~0ull, hi = 0ull;
-    for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < a.n_in; j += (int64_t)gridDim.x * blockDim.x) {
-        const unsigned long long o = jm::ord_i64(a.in.start[j]);
-        lo = o < lo ? o : lo;
-        hi = o > hi ? o : hi;
-    }
-    wave_minmax(lo, hi, &a.ctr->ts_min, &a.ctr->ts_max);
-}
-
-// Pass 2: route every record and in-flight session to the bulk sort or the arrival-order sort. A block
-// owns a contiguous chunk of kRouteItems * blockDim elements and reserves its two output runs with one
-// atomic per list (a per-wave reservation on one counter serialised 1M waves per push: 12.8 ms on C5s).
-constexpr int kRouteItems = 16;
-__device__ __forceinline__ void route_elem(const Sess2Args& a, int64_t t, bool& valid, bool& sp, unsigned long long& bk,
-                                           unsigned long long& sk, uint32_t& pay) {
-    valid = false; sp = false; bk = 0; sk = 0; pay = 0;
-    if (t < a.n) {
-        const uint32_t kid = a.rkid[t];
-        if (kid == 0xffffffffu) return;
-        valid = true;
-        sp = a.all_sp || a.kflag[kid];
-        pay = (uint32_t)t;
-        bk = ((unsigned long long)kid << a.tb) | (uint64_t)(a.ts[t] - a.base);
-        sk = ((unsigned long long)kid << 32) | (uint64_t)(t + 1);
-    } else if (t < a.n + a.n_in) {
-        const int64_t j = t - a.n;
-        const uint32_t kid = a.in.kid[j];
-        valid = true;
-        sp = a.all_sp || a.kflag[kid];
-        pay = (uint32_t)j | 0x80000000u;
-        bk = ((unsigned long long)kid << a.tb) | (uint64_t)(a.in.start[j] - a.base);
-        sk = (unsigned long long)kid << 32;
-    }
-}
-
-__global__ void __launch_bounds__(kBlock) sess2_route_kernel(Sess2Args a, const EngineConst* __restrict__ cp) {
-    constexpr int kW = kBlock / 64;
-    __shared__ uint32_t s_wb[kW], s_ws[kW];
-    __shared__ unsigned long long s_base[2];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int64_t c0 = (int64_t)blockIdx.x * kBlock * kRouteItems;
-    uint32_t nbk = 0, nsp = 0;
-    for (int j = 0; j < kRouteItems; ++j) {
-        bool valid, sp; unsigned long long bk, sk; uint32_t pay;
-        route_elem(a, c0 + (int64_t)j * kBlock + threadIdx.x, valid, sp, bk, sk, pay);
-        nbk += (uint32_t)__popcll(__ballot(valid && !sp));
-        nsp += (uint32_t)__popcll(__ballot(valid && sp));
-    }
-    if (lane == 0) { s_wb[wv] = nbk; s_ws[wv] = nsp; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t tb = 0, ts = 0;
-        for (int w = 0; w < kW; ++w) { const uint32_t x = s_wb[w], y = s_ws[w]; s_wb[w] = tb; s_ws[w] = ts; tb += x; ts += y; }
-        s_base[0] = tb ? atomicAdd(&a.ctr->n_bulk, (unsigned long long)tb) : 0ull;
-        s_base[1] = ts ? atomicAdd(&a.ctr->n_sp, (unsigned long long)ts) : 0ull;
-    }
-    __syncthreads();
-    unsigned long long pb = s_base[0] + s_wb[wv], ps = s_base[1] + s_ws[wv];
-    const unsigned long long lt = (1ull << lane) - 1;
-    for (int j = 0; j < kRouteItems; ++j) {
-        bool valid, sp; unsigned long long bk, sk; uint32_t pay;
-        route_elem(a, c0 + (int64_t)j * kBlock + threadIdx.x, valid, sp, bk, sk, pay);
-        const unsigned long long mb = __ballot(valid && !sp), ms = __ballot(valid && sp);
-        if (valid && !sp) {
-            const unsigned long long o = pb + __popcll(mb & lt);
-            a.bkey[o] = bk;
-            const bool sess = (pay & 0x80000000u) != 0;
-            const bool flag = sess || a.gapc;
-            a.bval[o] = (uint32_t)o | (flag ? 0x80000000u : 0u);
-            unsigned long long* row = a.pk + (int64_t)o * a.pkw;
-            const int64_t x = (int64_t)(pay & 0x7fffffffu);
-            const EngineConst& c = *cp;
-            auto word = [&](int cc) -> unsigned long long {
-                if (sess) return a.in.acc[(int64_t)cc * a.in.stride + x];
-                if (cc == 0) return 1ull;
-                const AggDesc& d = c.agg[a.col_owner[cc]];
-                return acc_input(d, a.cols[d.col], x, a.nulls[d.col]);
-            };
-            int cc = 0;
-            if ((a.pkw & 1) == 0)                                  // 16-byte stores (rows stay 16-byte aligned)
-                for (; cc < a.pkw; cc += 2) *reinterpret_cast<ulonglong2*>(row + cc) = make_ulonglong2(word(cc), word(cc + 1));
-            for (; cc < a.pkw; ++cc) row[cc] = word(cc);
-            if (sess) a.pe[o] = a.in.end[x];
-            else if (a.gapc) a.pe[o] = jm::wadd(a.ts[x], a.gapc[x]);
-        }
-        if (valid && sp) { const unsigned long long o = ps + __popcll(ms & lt); a.skey[o] = sk; a.sval[o] = pay; }
-        pb += __popcll(mb);
-        ps += __popcll(ms);
-    }
-}
-
-// Bulk: end of every sorted element (records: start + gap; sessions: their end).
-__global__ void __launch_bounds__(kBlock) sess2_ends_kernel(Sess2Args a) {
-    const uint64_t smask = a.tb >= 64 ? ~0ull : (((uint64_t)1 << a.tb) - 1);
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.nb; i += (int64_t)gridDim.x * blockDim.x) {
-        const uint32_t p = a.bval[i];
-        const int64_t start = a.base + (int64_t)(a.bkey[i] & smask);
-        a.bend[i] = (p & 0x80000000u) ? a.pe[p & 0x7fffffffu] : jm::wadd(start, a.gap);
-    }
-}
-
-// Bulk: head flag = first element of a key, or start after every earlier end of the key.
-__global__ void __launch_bounds__(kBlock) sess2_heads_kernel(Sess2Args a) {
-    const uint64_t smask = (((uint64_t)1 << a.tb) - 1);
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.nb; i += (int64_t)gridDim.x * blockDim.x) {
-        uint32_t h = 1;
-        if (i > 0) {
-            const unsigned long long k = a.bkey[i], kp = a.bkey[i - 1];
-            h = ((k >> a.tb) != (kp >> a.tb) || a.base + (int64_t)(k & smask) > a.bmax[i - 1]) ? 1u : 0u;
-        }
-        a.bcid[i] = h;
-    }
-}
-
-
-__device__ __forceinline__ void acc_atomic(int acc_kind, unsigned long long* p, unsigned long long v) {
-    switch (acc_kind) {
-        case ACC_NONE: case ACC_ADD_I64: atomicAdd(p, v); break;
-        case ACC_ADD_F64: atomicAdd((double*)p, __longlong_as_double((long long)v)); break;
-        case ACC_MIN_ORD: atomicMin(p, v); break;
-        case ACC_MAX_ORD: atomicMax(p, v); break;
-        default: break;
-    }
-}
-
-__global__ void __launch_bounds__(kBlock) sess2_init_kernel(Sess2Args a, const EngineConst* __restrict__ cp) {
-    const EngineConst& c = *cp;
-    const int64_t ncl = a.nb > 0 ? (int64_t)a.bcid[a.nb - 1] : 0;
-    for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < ncl; j += (int64_t)gridDim.x * blockDim.x)
-        for (int cc = 0; cc < c.nacc; ++cc) a.out.acc[(int64_t)cc * a.out.stride + j] = cc == 0 ? 0ull : ident_of(c.acc_kind[cc]);
-}
-
-// Bulk: wave-segmented reduction of each cluster (COUNT + accumulator columns). The cluster's true
-// head writes kid and start, its true tail the end (= the key's running max end there); accumulators
-// of a cluster that lies inside one wave are written with plain stores, a cluster spanning waves is
-// combined into identity-initialised columns with atomics.
-__global__ void __launch_bounds__(kBlock) sess2_reduce_kernel(Sess2Args a, const EngineConst* __restrict__ cp) {
-    const EngineConst& c = *cp;
-    const int lane = threadIdx.x & 63;
-    const uint64_t smask = (((uint64_t)1 << a.tb) - 1);
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t w0 = (int64_t)blockIdx.x * blockDim.x; w0 < a.nb; w0 += stride) {   // uniform trips per wave
-        const int64_t wb = w0 + (threadIdx.x & ~63);     // this wave's first element
-        const int64_t i = w0 + threadIdx.x;
-        const bool act = i < a.nb;
-        const int64_t cid = act ? (int64_t)a.bcid[i] : -1 - lane;   // inactive lanes: distinct ids
-        const uint32_t p = act ? a.bval[i] : 0u;
-        const int64_t cid0 = __shfl(cid, 0);
-        const bool head0 = wb < a.nb && (wb == 0 || a.bcid[wb] != a.bcid[wb - 1]);
-        const int64_t cn = __shfl_down(cid, 1);
-        const bool last = act && (i + 1 >= a.nb || a.bcid[i + 1] != (uint32_t)cid);   // cluster's true tail
-        const bool tail = act && (lane == 63 || cn != cid);                          // its last lane here
-        const bool whole = (cid != cid0 || head0) && (lane != 63 || last);
-        const int64_t cl = cid - 1;
-        if (act && (i == 0 || a.bcid[i - 1] != (uint32_t)cid)) {
-            a.out.kid[cl] = (uint32_t)(a.bkey[i] >> a.tb);
-            a.out.start[cl] = a.base + (int64_t)(a.bkey[i] & smask);
-        }
-        if (last) a.out.end[cl] = a.bmax[i];
-        for (int cc = 0; cc < c.nacc; ++cc) {
-            const int ak = cc == 0 ? ACC_ADD_I64 : c.acc_kind[cc];
-            unsigned long long v = act ? a.pk[(int64_t)(p & 0x7fffffffu) * a.pkw + cc] : 0ull;
-            for (int d = 1; d < 64; d <<= 1) {
-                const unsigned long long y = __shfl_up(v, d);
-                const int64_t yc = __shfl_up(cid, d);
-                if (lane >= d && yc == cid) v = acc_combine(ak, v, y);
-            }
-            if (!tail) continue;
-            unsigned long long* dst = &a.out.acc[(int64_t)cc * a.out.stride + cl];
-            if (whole) *dst = v;
-            else acc_atomic(ak, dst, v);
-        }
-    }
-}
-
-// Bulk sessions after the (kid, start) sort in one pass, replacing ends / scan-by-key / heads / cluster-id scan /
-// reduce: wave w owns the keys whose first sorted element lies in positions [64w, 64w + 64) and walks each owned key
-// to its end in 64-element chunks, carrying the open cluster (the session being built) from chunk to chunk. Per chunk:
-// the ends (start + gap, or the element's own end), the key's running max end (segmented shuffle scan; lane 0 joins
-// the carried key), cluster heads (a new key, or a start after every earlier end of the key: TimeWindow.intersects is
-// inclusive, so touching windows merge), the accumulators per cluster (segmented shuffle scans over the packed
-// rows) and the completed clusters appended to the output list (one reservation per wave and chunk).
-template <int NA>
-__global__ void __launch_bounds__(kBlock) sess2_segment_kernel(Sess2Args a, const EngineConst* __restrict__ cp) {
-    const EngineConst& c = *cp;
-    const int lane = threadIdx.x & 63;
-    const uint64_t smask = ((uint64_t)1 << a.tb) - 1;              // tb <= 63 - kid bits on this path
-    const int64_t nb = a.nb;
-    const int64_t nw = (nb + 63) >> 6;
-    const int64_t wstride = ((int64_t)gridDim.x * blockDim.x) >> 6;
-    int ak[NA];
-#pragma unroll
-    for (int cc = 0; cc < NA; ++cc) ak[cc] = cc == 0 ? ACC_ADD_I64 : c.acc_kind[cc];
-    const unsigned long long below = lane == 63 ? ~0ull : ((2ull << lane) - 1ull);   // lanes <= this one
-    for (int64_t w = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6; w < nw; w += wstride) {
-        const int64_t p0 = w << 6;
-        // a window of 128 sorted positions (this wave's 64 and the next 64) and the element before, loaded at once:
-        // the heads, the end of the last owned key and the first two chunks come from it (one round trip)
-        const int64_t pa = p0 + lane, pb = p0 + 64 + lane;
-        const unsigned long long kA = pa < nb ? a.bkey[pa] : 0ull, kB = pb < nb ? a.bkey[pb] : 0ull;
-        const uint32_t vA = pa < nb ? a.bval[pa] : 0u, vB = pb < nb ? a.bval[pb] : 0u;
-        const unsigned long long kprev = p0 > 0 ? a.bkey[p0 - 1] : 0ull;
-        const uint32_t kidA = (uint32_t)(kA >> a.tb), kidB = (uint32_t)(kB >> a.tb);
-        const uint32_t kup = __shfl_up(kidA, 1);
-        const bool hd = pa < nb && (lane == 0 ? (p0 == 0 || (uint32_t)(kprev >> a.tb) != kidA) : kidA != kup);
-        const unsigned long long hm = __ballot(hd);
-        if (!hm) {                                                  // inside a key owned by an earlier wave
-            if (lane == 0) a.sg_cnt[w] = 0u;
-            continue;
-        }
-        const int64_t h0 = p0 + (__ffsll((long long)hm) - 1);
-        uint32_t wc = 0;                                            // clusters this wave wrote (staging h0 + i)
-        int64_t h1 = min(p0 + 64, nb);
-        if (h1 < nb) {                                              // the last owned key may run past the range
-            const uint32_t kl = __shfl(kidA, 63);
-            const unsigned long long dm = __ballot(pb >= nb || kidB != kl);
-            if (dm) h1 = p0 + 64 + (__ffsll((long long)dm) - 1);
-            else
-                for (int64_t q = p0 + 128;; q += 64) {
-                    const int64_t pp = q + lane;
-                    const unsigned long long dq = __ballot(pp >= nb || (uint32_t)(a.bkey[pp] >> a.tb) != kl);
-                    if (dq) { h1 = q + (__ffsll((long long)dq) - 1); break; }
-                }
-        }
-        // chunk loads: key, payload, end, accumulator row of position base + lane (window or memory)
-        auto fetch = [&](int64_t base, unsigned long long& bk, uint32_t& pay, int64_t& en, unsigned long long* x) {
-            const int64_t q = base + lane;
-            const int64_t d = q - p0;
-            if (base + 63 - p0 < 128) {                             // inside the window
-                const int src = (int)(d & 63);
-                const unsigned long long ka = __shfl(kA, src), kb = __shfl(kB, src);
-                const uint32_t va = __shfl(vA, src), vb = __shfl(vB, src);
-                bk = d < 64 ? ka : kb;
-                pay = d < 64 ? va : vb;
-            } else {
-                bk = q < h1 ? a.bkey[q] : 0ull;
-                pay = q < h1 ? a.bval[q] : 0u;
-            }
-            const bool v = q < h1;
-            const int64_t st = a.base + (int64_t)(bk & smask);
-            en = !v ? LONG_MIN_J : (pay & 0x80000000u) ? a.pe[pay & 0x7fffffffu] : jm::wadd(st, a.gap);
-            const uint32_t o = pay & 0x7fffffffu;
-#pragma unroll
-            for (int cc = 0; cc < NA; ++cc) x[cc] = v ? a.pk[(int64_t)o * a.pkw + cc] : 0ull;
-        };
-        uint32_t ck = 0u;                                           // the carried open cluster
-        int64_t cmax = LONG_MIN_J, cst = 0;
-        unsigned long long cacc[NA];
-#pragma unroll
-        for (int cc = 0; cc < NA; ++cc) cacc[cc] = 0ull;
-        bool copen = false;
-        unsigned long long nbk, nx[NA];                             // the next chunk, in flight (software pipeline)
-        uint32_t npay;
-        int64_t nen;
-        fetch(h0, nbk, npay, nen, nx);
-        for (int64_t base = h0; base < h1; base += 64) {
-            const int64_t q = base + lane;
-            const bool v = q < h1;
-            const unsigned long long bk = nbk;
-            const int64_t en = nen;
-            unsigned long long acc[NA];
-#pragma unroll
-            for (int cc = 0; cc < NA; ++cc) acc[cc] = nx[cc];
-            if (base + 64 < h1) fetch(base + 64, nbk, npay, nen, nx);
-            const uint32_t kk = (uint32_t)(bk >> a.tb);
-            const int64_t st = a.base + (int64_t)(bk & smask);
-            const uint32_t kp = __shfl_up(kk, 1);
-            const bool kc = v && (lane == 0 ? (!copen || kk != ck) : kk != kp);
-            const unsigned long long km = __ballot(kc) & below;
-            const int ks = km ? 63 - __clzll((long long)km) : 0;   // first lane of this lane's key in the chunk
-            int64_t m = en;                                         // running max end of the key (inclusive)
-            for (int d = 1; d < 64; d <<= 1) {
-                const int64_t y = __shfl_up(m, d);
-                if (lane - d >= ks && y > m) m = y;
-            }
-            if (km == 0 && copen && cmax > m) m = cmax;            // the key continues from the previous chunk
-            int64_t mprev = __shfl_up(m, 1);
-            if (lane == 0) mprev = cmax;
-            const bool head = v && (kc || st > mprev);
-            const unsigned long long hb = __ballot(head) & below;
-            const int cs = hb ? 63 - __clzll((long long)hb) : 0;   // first lane of this lane's cluster in the chunk
-            const bool ccont = hb == 0;                            // still the carried cluster
-            const int64_t hst = __shfl(st, cs);
-            const int64_t cstart = ccont ? cst : hst;
-#pragma unroll
-            for (int cc = 0; cc < NA; ++cc) {
-                unsigned long long x = acc[cc];
-                for (int d = 1; d < 64; d <<= 1) {
-                    const unsigned long long y = __shfl_up(x, d);
-                    if (lane - d >= cs) x = acc_combine(ak[cc], x, y);
-                }
-                if (ccont && copen) x = acc_combine(ak[cc], cacc[cc], x);
-                acc[cc] = x;
-            }
-            const bool nxt = __shfl_down(head ? 1 : 0, 1) != 0;
-            const bool tail = v && (q + 1 == h1 || (lane < 63 && nxt));
-            const bool emit_c = copen && __shfl(head ? 1 : 0, 0) != 0;   // the carried cluster ended before lane 0
-            if (emit_c && lane == 0) {
-                const int64_t sc = h0 + (int64_t)wc;
-                a.sg_kid[sc] = ck;
-                a.sg_start[sc] = cst;
-                a.sg_end[sc] = cmax;
-#pragma unroll
-                for (int cc = 0; cc < NA; ++cc) a.sg_acc[(int64_t)cc * a.sg_cap + sc] = cacc[cc];
-            }
-            wc += emit_c ? 1u : 0u;
-            const unsigned long long tm = __ballot(tail);
-            if (tail) {
-                const int64_t so = h0 + (int64_t)wc + __popcll(tm & ((1ull << lane) - 1ull));
-                a.sg_kid[so] = kk;
-                a.sg_start[so] = cstart;
-                a.sg_end[so] = m;                                   // the key's max end at the cluster's last element
-#pragma unroll
-                for (int cc = 0; cc < NA; ++cc) a.sg_acc[(int64_t)cc * a.sg_cap + so] = acc[cc];
-            }
-            wc += (uint32_t)__popcll(tm);
-            ck = __shfl(kk, 63);
-            cmax = __shfl(m, 63);
-            cst = __shfl(cstart, 63);
-#pragma unroll
-            for (int cc = 0; cc < NA; ++cc) cacc[cc] = __shfl(acc[cc], 63);
-            copen = true;
-        }
-        if (lane == 0) { a.sg_cnt[w] = wc; a.sg_h0[w] = h0; }
-    }
-}
-
-// The segment kernel's clusters, moved from each wave's staging range to the output list at the exclusive sum of the
-// per-wave counts (one thread per wave; the arrival-order path appends after them on ctr->n_out_sp).
-// One thread per output session (coalesced stores): the staging wave w that owns output dst is the last one with
-// sg_off[w] <= dst (a binary search over the scanned counts, which stay cache-resident); a thread per wave copying its
-// ~1.4 clusters serially took 0.24 ms per C5s push.
-__global__ void __launch_bounds__(kBlock) sess2_compact_kernel(Sess2Args a, int64_t nw, int nacc) {
-    const int64_t tot = a.sg_off[nw];
-    for (int64_t dst = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; dst < tot; dst += (int64_t)gridDim.x * blockDim.x) {
-        int64_t lo = 0, hi = nw;                          // invariant: sg_off[lo] <= dst < sg_off[hi]
-        while (hi - lo > 1) {
-            const int64_t mid = (lo + hi) >> 1;
-            if ((int64_t)a.sg_off[mid] <= dst) lo = mid; else hi = mid;
-        }
-        const int64_t src = a.sg_h0[lo] + (dst - (int64_t)a.sg_off[lo]);
-        a.out.kid[dst] = a.sg_kid[src];
-        a.out.start[dst] = a.sg_start[src];
-        a.out.end[dst] = a.sg_end[src];
-        for (int cc = 0; cc < nacc; ++cc) a.out.acc[(int64_t)cc * a.out.stride + dst] = a.sg_acc[(int64_t)cc * a.sg_cap + src];
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) a.ctr->n_out_sp = (unsigned long long)tot;
-}
-
-// ---- Cell path: fixed gap, every record of the push order-free ------------------------------------------------------
-// The time axis is cut into cells of width gap starting at base = the smallest start of the push. Two windows whose
-// starts lie in one cell intersect (s2 - s1 < gap <= end1 - s1, TimeWindow.intersects), so the elements of one
-// (kid, cell) group end in one session whatever their order: sorting by the 32-bit key kid << cb | cell (cb = 32 -
-// kid_bits) replaces the (kid, start) sort (4 one-byte passes over 8-byte pairs instead of 5 over 12-byte pairs), and
-// the segment walk reduces each group (min start, max end, accumulators) before chaining the key's groups in cell
-// order. Records go to the sort at their input position (no compaction); a record that is not order-free or a start
-// outside the cell range is counted and the host redoes the push on the general path (sess2_*).
-constexpr uint32_t kCellSent = 0xffffffffu;        // sorts last; its kid (all ones in kid_bits) is never a real kid
-
-__global__ void __launch_bounds__(kBlock) sess3_min_kernel(Sess2Args a) {
-    __shared__ unsigned long long s_lo[kBlock / 64];
-    unsigned long long lo = ~0ull;
-    const int64_t tot = a.n + a.n_in;
-    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < tot; t += (int64_t)gridDim.x * blockDim.x) {
-        const unsigned long long o = jm::ord_i64(t < a.n ? a.ts[t] : a.in.start[t - a.n]);
-        lo = o < lo ? o : lo;
-    }
-    for (int sh = 32; sh >= 1; sh >>= 1) { const unsigned long long y = __shfl_xor(lo, sh); lo = y < lo ? y : lo; }
-    if ((threadIdx.x & 63) == 0) s_lo[threadIdx.x >> 6] = lo;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < kBlock / 64; ++w) lo = s_lo[w] < lo ? s_lo[w] : lo;
-        if (lo != ~0ull) atomicMin(&a.ctr->ts_min, lo);
-    }
-}
-
-// Probe of the key's first 8-slot bucket (one 64-byte read); -1 when the key is not there (then key_slot, which also
-// inserts). Loads only: the caller issues several before using any.
-__device__ __forceinline__ int64_t key_probe8(const unsigned long long* table, int seg_log, int part_bits, int64_t key,
-                                             ulonglong2 (&bk)[4], uint64_t& i0) {
-    const uint64_t h = jm::mix64((uint64_t)key);
-    const uint64_t smask = ((uint64_t)1 << seg_log) - 1;
-    i0 = seg_base(h, seg_log, part_bits) | (h & smask & ~(uint64_t)(kBucket - 1));
-    const ulonglong2* p = reinterpret_cast<const ulonglong2*>(table + i0);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) bk[j] = p[j];
-    return 0;
-}
-__device__ __forceinline__ int64_t key_probe8_find(const ulonglong2 (&bk)[4], uint64_t i0, int64_t key) {
-    const unsigned long long k = (unsigned long long)key;
-    int64_t r = -1;
-#pragma unroll
-    for (int j = 3; j >= 0; --j) {
-        if (bk[j].y == k) r = (int64_t)(i0 + 2 * j + 1);
-        if (bk[j].x == k) r = (int64_t)(i0 + 2 * j);
-    }
-    return r;
-}
-
-// Records: block b routes its chunk [b * chunk, (b + 1) * chunk): key-group check, kid (U records' bucket probes in
-// flight at once), 32-bit cell key and payload (the row position) at the record's input position, and the packed row
-// [ts, acc_1 .. acc_{nacc-1}] (COUNT is 1 for a record) at the same position.
-template <int U>
-__global__ void __launch_bounds__(kBlock) sess3_route_kernel(Sess2Args a, const EngineConst* __restrict__ cp, int64_t chunk) {
-    __shared__ uint32_t s_c[2];
-    const EngineConst& c = *cp;
-    if (threadIdx.x == 0) { s_c[0] = 0u; s_c[1] = 0u; }
-    __syncthreads();
-    const int cb = a.tb;
-    const uint64_t ncell = (uint64_t)1 << cb;
-    const uint64_t base = (uint64_t)jm::unord_i64(a.ctr->ts_min);
-    uint32_t nsp = 0, nredo = 0;
-    uint32_t* bkey = reinterpret_cast<uint32_t*>(a.bkey);
-    const int64_t r0 = (int64_t)blockIdx.x * chunk, r1 = min(a.n, r0 + chunk);
-    for (int64_t t0 = r0 + threadIdx.x; t0 < r1; t0 += (int64_t)blockDim.x * U) {
-        int64_t key[U], ts[U], kid[U];
-        ulonglong2 bk[U][4];
-        uint64_t i0[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int64_t t = t0 + (int64_t)u * blockDim.x;
-            key[u] = t < r1 ? a.keys[t] : 0;
-            ts[u] = t < r1 ? a.ts[t] : 0;
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) key_probe8(a.key_table, a.seg_log, a.part_bits, key[u], bk[u], i0[u]);
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int64_t t = t0 + (int64_t)u * blockDim.x;
-            if (t >= r1) continue;
-            uint32_t k32 = kCellSent;
-            kid[u] = -1;
-            const int32_t kg = jm::key_group_of(key[u], c.key_kind, a.key_hash ? a.key_hash[t] : 0, c.max_par);
-            if (kg < c.kg_lo || kg > c.kg_hi) {
-                raise_error(a.st, FWA_E_KEYGROUP);                     // StateTable :300-307
-            } else {
-                kid[u] = (uint64_t)key[u] == kEmptyKey ? -1 : key_probe8_find(bk[u], i0[u], key[u]);
-                if (kid[u] < 0) kid[u] = key_slot(a.key_table, a.key_mask, a.seg_log, a.part_bits, key[u], a.st);
-                if (kid[u] < 0) {
-                    a.st->key_full = 1;
-                    raise_error(a.st, FWA_E_OOM);
-                } else if (jm::wsub(jm::wadd(ts[u], a.gap), 1) <= a.wm) {   // order-sensitive: the general path
-                    a.kflag[kid[u]] = 1;
-                    ++nsp;
-                } else {
-                    const uint64_t cell = jm::udiv64((uint64_t)ts[u] - base, a.gap_div);
-                    if (cell >= ncell) ++nredo;
-                    else k32 = ((uint32_t)kid[u] << cb) | (uint32_t)cell;
-                }
-            }
-            uint32_t pos = 0u;
-            if (k32 != kCellSent) {
-                pos = (uint32_t)t;
-                unsigned long long* row = a.pk + (int64_t)pos * a.pkw;
-                const int64_t tsu = ts[u];
-                auto word = [&](int cc) -> unsigned long long {
-                    if (cc == 0) return (unsigned long long)tsu;
-                    const AggDesc& d = c.agg[a.col_owner[cc]];
-                    return acc_input(d, a.cols[d.col], t, a.nulls[d.col]);
-                };
-                int cc = 0;
-                if ((a.pkw & 1) == 0)
-                    for (; cc < a.pkw; cc += 2) *reinterpret_cast<ulonglong2*>(row + cc) = make_ulonglong2(word(cc), word(cc + 1));
-                for (; cc < a.pkw; ++cc) row[cc] = word(cc);
-            }
-            bkey[t] = k32;
-            a.bval[t] = pos;
-        }
-    }
-    for (int sh = 32; sh >= 1; sh >>= 1) { nsp += __shfl_xor(nsp, sh); nredo += __shfl_xor(nredo, sh); }
-    if ((threadIdx.x & 63) == 0 && (nsp | nredo)) { atomicAdd(&s_c[0], nsp); atomicAdd(&s_c[1], nredo); }
-    __syncthreads();
-    if (threadIdx.x == 0 && s_c[0]) atomicAdd(&a.ctr->n_special, (unsigned long long)s_c[0]);
-    if (threadIdx.x == 0 && s_c[1]) atomicAdd(&a.ctr->n_redo, (unsigned long long)s_c[1]);
-}
-
-// In-flight sessions at sort positions n + j: cell key of their start, payload j | 0x80000000.
-__global__ void __launch_bounds__(kBlock) sess3_route_sessions_kernel(Sess2Args a) {
-    const int cb = a.tb;
-    const uint64_t ncell = (uint64_t)1 << cb;
-    const uint64_t base = (uint64_t)jm::unord_i64(a.ctr->ts_min);
-    uint32_t* bkey = reinterpret_cast<uint32_t*>(a.bkey);
-    uint32_t nredo = 0;
-    for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < a.n_in; j += (int64_t)gridDim.x * blockDim.x) {
-        const uint64_t cell = jm::udiv64((uint64_t)a.in.start[j] - base, a.gap_div);
-        uint32_t k32 = kCellSent;
-        if (cell >= ncell) ++nredo;
-        else k32 = (a.in.kid[j] << cb) | (uint32_t)cell;
-        bkey[a.n + j] = k32;
-        a.bval[a.n + j] = (uint32_t)j | 0x80000000u;
-    }
-    for (int sh = 32; sh >= 1; sh >>= 1) nredo += __shfl_xor(nredo, sh);
-    if ((threadIdx.x & 63) == 0 && nredo) atomicAdd(&a.ctr->n_redo, (unsigned long long)nredo);
-}
-
-__device__ __forceinline__ uint32_t perm32(int dst4, uint32_t v) { return (uint32_t)__builtin_amdgcn_ds_permute(dst4, (int)v); }
-__device__ __forceinline__ unsigned long long perm64(int dst4, unsigned long long v) {
-    const uint32_t lo = perm32(dst4, (uint32_t)v), hi = perm32(dst4, (uint32_t)(v >> 32));
-    return ((unsigned long long)hi << 32) | lo;
-}
-
-// Cross-lane moves on the VALU (DPP) instead of the LDS crossbar: row_shr:n = 0x110 + n, row_bcast:15 = 0x142,
-// row_bcast:31 = 0x143, wave_shl:1 = 0x130, wave_shr:1 = 0x138 (lanes without a source get 0)
-template <int CTRL, int RM = 0xf>
-__device__ __forceinline__ uint32_t dpp32(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, RM, 0xf, false);
-}
-template <int CTRL, int RM = 0xf>
-__device__ __forceinline__ unsigned long long dpp64(unsigned long long v) {
-    return ((unsigned long long)dpp32<CTRL, RM>((uint32_t)(v >> 32)) << 32) | dpp32<CTRL, RM>((uint32_t)v);
-}
-__device__ __forceinline__ unsigned long long rdlane64(unsigned long long v, int l) {   // wave-uniform l
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, l);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), l);
-    return ((unsigned long long)hi << 32) | lo;
-}
-__device__ __forceinline__ uint32_t rdlane32(uint32_t v, int l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, l); }
-
-// Segmented inclusive scans: lane L combines the lanes [gs(L), L] (gs = first lane of L's segment) with the earlier
-// part as the second operand. Hillis-Steele inside rows of 16 (row_shr 1, 2, 4, 8), then the row totals (row_bcast 15
-// / 31); one accumulator kind per scan, branch-free (selects; the kind switch is taken once per scan, not per step).
-template <int K>
-__device__ __forceinline__ unsigned long long comb_k(unsigned long long x, unsigned long long y) {
-    if constexpr (K == ACC_ADD_I64) return x + y;
-    else if constexpr (K == ACC_ADD_F64)
-        return (unsigned long long)__double_as_longlong(__longlong_as_double((long long)x) + __longlong_as_double((long long)y));
-    else if constexpr (K == ACC_MIN_ORD) return y < x ? y : x;
-    else if constexpr (K == ACC_MAX_ORD) return y > x ? y : x;
-    else return x;
-}
-template <int K>
-__device__ __forceinline__ unsigned long long seg_scan_k(unsigned long long x, int lane, int gs) {
-    unsigned long long y, r;
-    y = dpp64<0x111>(x); r = comb_k<K>(x, y); x = ((lane & 15) >= 1 && lane - 1 >= gs) ? r : x;
-    y = dpp64<0x112>(x); r = comb_k<K>(x, y); x = ((lane & 15) >= 2 && lane - 2 >= gs) ? r : x;
-    y = dpp64<0x114>(x); r = comb_k<K>(x, y); x = ((lane & 15) >= 4 && lane - 4 >= gs) ? r : x;
-    y = dpp64<0x118>(x); r = comb_k<K>(x, y); x = ((lane & 15) >= 8 && lane - 8 >= gs) ? r : x;
-    y = dpp64<0x142, 0xa>(x); r = comb_k<K>(x, y); x = ((lane & 16) != 0 && gs < (lane & ~15)) ? r : x;
-    y = dpp64<0x143, 0xc>(x); r = comb_k<K>(x, y); x = (lane >= 32 && gs < 32) ? r : x;
-    return x;
-}
-__device__ __forceinline__ unsigned long long seg_scan_acc(int k, unsigned long long x, int lane, int gs) {
-    switch (k) {
-        case ACC_ADD_I64: return seg_scan_k<ACC_ADD_I64>(x, lane, gs);
-        case ACC_ADD_F64: return seg_scan_k<ACC_ADD_F64>(x, lane, gs);
-        case ACC_MIN_ORD: return seg_scan_k<ACC_MIN_ORD>(x, lane, gs);
-        case ACC_MAX_ORD: return seg_scan_k<ACC_MAX_ORD>(x, lane, gs);
-        default: return x;
-    }
-}
-__device__ __forceinline__ int64_t seg_min64(int64_t x, int lane, int gs) {   // ord encoding: unsigned min
-    return jm::unord_i64(seg_scan_k<ACC_MIN_ORD>(jm::ord_i64(x), lane, gs));
-}
-__device__ __forceinline__ int64_t seg_max64(int64_t x, int lane, int gs) {
-    return jm::unord_i64(seg_scan_k<ACC_MAX_ORD>(jm::ord_i64(x), lane, gs));
-}
-
-// The cell-sorted elements in one pass. Ownership as in sess2_segment_kernel (wave w owns the keys whose first sorted
-// element lies in [64w, 64w + 64) and walks each to its end). Per 64-element chunk: (1) segmented scans over the
-// (kid, cell) groups -- min start, max end, accumulators -- joined with the group carried from the previous chunk;
-// (2) the groups that end in the chunk are packed to the low lanes (ds_permute) and chained as sess2_segment_kernel
-// chains elements: a group opens a session if it starts a key or starts after the key's running max end.
-template <int NA>
-__global__ void __launch_bounds__(kBlock) sess3_segment_kernel(Sess2Args a, const EngineConst* __restrict__ cp) {
-    const EngineConst& c = *cp;
-    const int lane = threadIdx.x & 63;
-    const int cb = a.tb;
-    const uint32_t* bkey = reinterpret_cast<const uint32_t*>(a.bkey);
-    const int64_t nb = a.nb;
-    const int64_t nw = (nb + 63) >> 6;
-    const int64_t wstride = ((int64_t)gridDim.x * blockDim.x) >> 6;
-    int ak[NA];
-    unsigned long long idn[NA];
-#pragma unroll
-    for (int cc = 0; cc < NA; ++cc) { ak[cc] = cc == 0 ? ACC_ADD_I64 : c.acc_kind[cc]; idn[cc] = ident_of(ak[cc]); }
-    const unsigned long long below = lane == 63 ? ~0ull : ((2ull << lane) - 1ull);   // lanes <= this one
-    const unsigned long long before = (1ull << lane) - 1ull;                          // lanes < this one
-    for (int64_t w = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6; w < nw; w += wstride) {
-        const int64_t p0 = w << 6;
-        const int64_t pa = p0 + lane, pb = p0 + 64 + lane;
-        const uint32_t kA = pa < nb ? bkey[pa] : kCellSent, kB = pb < nb ? bkey[pb] : kCellSent;
-        const uint32_t vA = pa < nb ? a.bval[pa] : 0u, vB = pb < nb ? a.bval[pb] : 0u;
-        const uint32_t kprev = p0 > 0 ? bkey[p0 - 1] : kCellSent;
-        const uint32_t kidA = kA >> cb;
-        const uint32_t kup = __shfl_up(kidA, 1);
-        const bool okA = kA != kCellSent;
-        const bool hd = okA && (lane == 0 ? (p0 == 0 || (kprev >> cb) != kidA) : kidA != kup);
-        const unsigned long long hm = __ballot(hd);
-        if (!hm) {
-            if (lane == 0) a.sg_cnt[w] = 0u;
-            continue;
-        }
-        const int64_t h0 = p0 + (__ffsll((long long)hm) - 1);
-        int64_t h1;
-        const unsigned long long sa = __ballot(!okA);               // sentinels / the end inside this range
-        if (sa) {
-            h1 = p0 + (__ffsll((long long)sa) - 1);
-        } else {                                                    // the last owned key may run past the range
-            const uint32_t kl = __shfl(kidA, 63);
-            const unsigned long long dm = __ballot((kB >> cb) != kl);   // a sentinel's kid differs from every kid
-            if (dm) h1 = p0 + 64 + (__ffsll((long long)dm) - 1);
-            else
-                for (int64_t q = p0 + 128;; q += 64) {
-                    const int64_t pp = q + lane;
-                    const uint32_t kq = pp < nb ? bkey[pp] : kCellSent;
-                    const unsigned long long dq = __ballot((kq >> cb) != kl);
-                    if (dq) { h1 = q + (__ffsll((long long)dq) - 1); break; }
-                }
-        }
-        auto fetch = [&](int64_t base, uint32_t& bk, int64_t& st, int64_t& en, unsigned long long* x) {
-            const int64_t q = base + lane;
-            const int64_t d = q - p0;
-            uint32_t pay;
-            if (base + 63 - p0 < 128) {                             // inside the loaded window
-                const int src = (int)(d & 63);
-                const uint32_t ka = __shfl(kA, src), kb = __shfl(kB, src);
-                const uint32_t va = __shfl(vA, src), vb = __shfl(vB, src);
-                bk = d < 64 ? ka : kb;
-                pay = d < 64 ? va : vb;
-            } else {
-                bk = q < h1 ? bkey[q] : kCellSent;
-                pay = q < h1 ? a.bval[q] : 0u;
-            }
-            const uint32_t o = pay & 0x7fffffffu;
-            if (q >= h1) {
-                bk = kCellSent;
-                st = LONG_MAX_J;
-                en = LONG_MIN_J;
-#pragma unroll
-                for (int cc = 0; cc < NA; ++cc) x[cc] = idn[cc];
-            } else if (pay & 0x80000000u) {                         // in-flight session
-                st = a.in.start[o];
-                en = a.in.end[o];
-#pragma unroll
-                for (int cc = 0; cc < NA; ++cc) x[cc] = a.in.acc[(int64_t)cc * a.in.stride + o];
-            } else {                                                // record: packed row [ts, acc_1 ..]
-                const unsigned long long* row = a.pk + (int64_t)o * NA;
-                unsigned long long wv[NA];
-                if constexpr ((NA & 1) == 0) {
-#pragma unroll
-                    for (int cc = 0; cc < NA; cc += 2) {
-                        const ulonglong2 p = reinterpret_cast<const ulonglong2*>(row)[cc >> 1];
-                        wv[cc] = p.x;
-                        wv[cc + 1] = p.y;
-                    }
-                } else {
-#pragma unroll
-                    for (int cc = 0; cc < NA; ++cc) wv[cc] = row[cc];
-                }
-                st = (int64_t)wv[0];
-                en = jm::wadd(st, a.gap);
-                x[0] = 1ull;
-#pragma unroll
-                for (int cc = 1; cc < NA; ++cc) x[cc] = wv[cc];
-            }
-        };
-        // Carries (wave-uniform): the pending group (its last element not seen yet: its session is undecided) and the
-        // open session (every group before the pending one that belongs to it).
-        bool gopen = false, copen = false;
-        uint32_t gkey = 0u, ck = 0u;
-        int64_t gmin = 0, gmax = 0, cmaxe = LONG_MIN_J, cst = 0;
-        unsigned long long gacc[NA], cacc[NA];
-#pragma unroll
-        for (int cc = 0; cc < NA; ++cc) { gacc[cc] = 0ull; cacc[cc] = 0ull; }
-        uint32_t wc = 0;                                            // sessions this wave wrote (staging h0 + i)
-        uint32_t nbk;
-        int64_t nst, nen;
-        unsigned long long nx[NA];
-        fetch(h0, nbk, nst, nen, nx);
-        for (int64_t base = h0; base < h1; base += 64) {
-            const int64_t q = base + lane;
-            const bool v = q < h1;
-            const uint32_t bk = nbk;
-            int64_t st = nst, en = nen;
-            unsigned long long x[NA];
-#pragma unroll
-            for (int cc = 0; cc < NA; ++cc) x[cc] = nx[cc];
-            const bool more = base + 64 < h1;
-            if (more) fetch(base + 64, nbk, nst, nen, nx);
-            // (1) groups: min start / max end per (kid, cell) run, joined with the pending group at lane 0
-            const uint32_t gup = dpp32<0x138>(bk);                  // lane - 1
-            const bool cont0 = gopen && rdlane32(bk, 0) == gkey;    // lane 0 continues the pending group
-            const bool gf = v && (lane == 0 ? !cont0 : bk != gup);
-            const unsigned long long GF = __ballot(gf);
-            const unsigned long long gm = GF & below;
-            const int gs = gm ? 63 - __clzll((long long)gm) : 0;
-            st = seg_min64(st, lane, gs);
-            en = seg_max64(en, lane, gs);
-            if (gm == 0 && cont0) {
-                st = gmin < st ? gmin : st;
-                en = gmax > en ? gmax : en;
-            }
-            const uint32_t nk0 = rdlane32(nbk, 0);                  // the next chunk's first key (when `more`)
-            const uint32_t gdn = dpp32<0x130>(bk);                  // lane + 1
-            const bool gt = v && (q + 1 == h1 || (lane < 63 ? gdn != bk : nk0 != bk));   // the group's last element
-            const int lv = (int)min<int64_t>(63, h1 - 1 - base);   // last valid lane
-            const unsigned long long P = __ballot(gt);
-            const bool pend = ((P >> lv) & 1ull) == 0;              // the last group continues in the next chunk
-            // (2) chain the groups that end here, packed to lanes [0, np): heads and session tails
-            const int np = __popcll(P);
-            uint32_t kk = 0u;
-            int64_t gst = 0, m = LONG_MIN_J, cstart = 0;
-            bool head = false, ptail = false;
-            unsigned long long H = 0ull;
-            if (np) {
-                const int dst = gt ? __popcll(P & before) : np + __popcll(~P & before);
-                kk = perm32(dst * 4, bk >> cb);
-                gst = (int64_t)perm64(dst * 4, (unsigned long long)st);
-                const int64_t gen = (int64_t)perm64(dst * 4, (unsigned long long)en);
-                const bool range_end = base + lv + 1 == h1;         // the last packed group closes the walk
-                const bool pv = lane < np;
-                const uint32_t kp = dpp32<0x138>(kk);
-                const bool kc = pv && (lane == 0 ? (!copen || kk != ck) : kk != kp);
-                const unsigned long long km = __ballot(kc) & below;
-                const int ks = km ? 63 - __clzll((long long)km) : 0;
-                m = seg_max64(pv ? gen : LONG_MIN_J, lane, ks);     // running max end of the key (inclusive)
-                if (km == 0 && copen && cmaxe > m) m = cmaxe;       // the key continues from the open session
-                int64_t mprev = (int64_t)dpp64<0x138>((unsigned long long)m);
-                if (lane == 0) mprev = cmaxe;
-                head = pv && (kc || gst > mprev);
-                H = __ballot(head);
-                const unsigned long long hb = H & below;
-                const int cs = hb ? 63 - __clzll((long long)hb) : 0;
-                const int64_t hst = __shfl(gst, cs);
-                cstart = hb == 0 ? cst : hst;
-                ptail = pv && (lane == np - 1 ? range_end : (lane < 63 && ((H >> ((lane + 1) & 63)) & 1ull) != 0));
-            }
-            // (3) accumulators once, per element, segmented by session: a segment starts at lane 0, at the first
-            // element of every head group, and at the first element of the pending group
-            const unsigned long long Pge = P & ~before;             // groups ending at or after this lane
-            const int tl = Pge ? __ffsll((long long)Pge) - 1 : 64;  // this lane's group tail (64: pending group)
-            const int rk = __popcll(P & ((tl < 64) ? ((1ull << tl) - 1ull) : ~0ull));   // its packed rank
-            const bool ghead = tl < 64 && ((H >> rk) & 1ull) != 0;
-            const unsigned long long SS = __ballot(v && gf && (tl == 64 || ghead)) | 1ull;
-            const unsigned long long sm = SS & below;
-            const int ss = 63 - __clzll((long long)sm);
-            // prefix of the first segment: the open session unless its first group is a head, then the pending group
-            // that lane 0 continues
-            const bool g0end = (P & ~0ull) != 0;                    // the group at lane 0 ends in this chunk
-            const bool pre_c = copen && g0end && (H & 1ull) == 0;
-            const bool pre_g = cont0;
-#pragma unroll
-            for (int cc = 0; cc < NA; ++cc) {
-                unsigned long long xx = seg_scan_acc(ak[cc], x[cc], lane, ss);
-                if (ss == 0 && pre_g) xx = acc_combine(ak[cc], xx, gacc[cc]);
-                if (ss == 0 && pre_c) xx = acc_combine(ak[cc], xx, cacc[cc]);
-                x[cc] = xx;
-            }
-            // the open session ended before the first group here
-            const bool emit_c = copen && np > 0 && (H & 1ull) != 0;
-            if (emit_c && lane == 0) {
-                const int64_t sc = h0 + (int64_t)wc;
-                a.sg_kid[sc] = ck;
-                a.sg_start[sc] = cst;
-                a.sg_end[sc] = cmaxe;
-#pragma unroll
-                for (int cc = 0; cc < NA; ++cc) a.sg_acc[(int64_t)cc * a.sg_cap + sc] = cacc[cc];
-            }
-            wc += emit_c ? 1u : 0u;
-            // sessions ending at an element lane (the tail of a packed group whose session ends)
-            const int rsrc = gt ? __popcll(P & before) : 0;
-            const int ptl = __shfl(ptail ? 1 : 0, rsrc);           // every lane takes part in the shuffle
-            const bool etail = gt && ptl != 0;
-            const int64_t e_start = __shfl(cstart, rsrc);
-            const int64_t e_end = __shfl(m, rsrc);
-            const unsigned long long tm = __ballot(etail);
-            if (etail) {
-                const int64_t so = h0 + (int64_t)wc + __popcll(tm & before);
-                a.sg_kid[so] = bk >> cb;
-                a.sg_start[so] = e_start;
-                a.sg_end[so] = e_end;
-#pragma unroll
-                for (int cc = 0; cc < NA; ++cc) a.sg_acc[(int64_t)cc * a.sg_cap + so] = x[cc];
-            }
-            wc += (uint32_t)__popcll(tm);
-            // carries
-            if (np) {
-                const int tlast = 63 - __clzll((long long)P);       // element lane of the last ended group
-                ck = rdlane32(kk, np - 1);
-                cmaxe = (int64_t)rdlane64((unsigned long long)m, np - 1);
-                cst = (int64_t)rdlane64((unsigned long long)cstart, np - 1);
-#pragma unroll
-                for (int cc = 0; cc < NA; ++cc) cacc[cc] = rdlane64(x[cc], tlast);
-                copen = true;
-            }
-            gopen = pend;
-            if (pend) {
-                gkey = rdlane32(bk, lv);
-                gmin = (int64_t)rdlane64((unsigned long long)st, lv);
-                gmax = (int64_t)rdlane64((unsigned long long)en, lv);
-#pragma unroll
-                for (int cc = 0; cc < NA; ++cc) gacc[cc] = rdlane64(x[cc], lv);
-            }
-        }
-        if (lane == 0) { a.sg_cnt[w] = wc; a.sg_h0[w] = h0; }
-    }
-}
-
-__device__ __forceinline__ int64_t sess_key_of(const unsigned long long* key_table, int64_t capacity, uint32_t kid) {
-    return (int64_t)kid < capacity ? (int64_t)key_table[kid] : LONG_MIN_J;   // side slot: the sentinel key
-}
-
-// Arrival-order path: one lane per key run of the (kid, arrival)-sorted list; its in-flight sessions
-// come first (low word 0), then its records in arrival order. The run's scratch region [t, t + len)
-// holds its session list (a run of len elements never has more than len sessions).
-__global__ void __launch_bounds__(kBlock) sess2_ordered_kernel(Sess2Args a, const EngineConst* __restrict__ cp) {
-    const EngineConst& c = *cp;
-    const int nacc = c.nacc;
-    const bool table = c.sem == FWA_SEM_TABLE;
-    const int64_t ncl = (a.seg_out || a.nb == 0) ? 0 : (int64_t)a.bcid[a.nb - 1];
-    unsigned long long dropped = 0;
-    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < a.nsp; t += (int64_t)gridDim.x * blockDim.x) {
-        const uint32_t kid = (uint32_t)(a.skey[t] >> 32);
-        if (t > 0 && (uint32_t)(a.skey[t - 1] >> 32) == kid) continue;   // not the head of the key's run
-        int64_t* ss = a.sc_start + t;
-        int64_t* se = a.sc_end + t;
-        auto acc = [&](int cc, int64_t s) -> unsigned long long& { return a.sc_acc[(int64_t)cc * a.nsp + t + s]; };
-        int64_t ns = 0;
-        bool failed = false;
-        for (int64_t j = t; j < a.nsp && (uint32_t)(a.skey[j] >> 32) == kid && !failed; ++j) {
-            const uint32_t p = a.sval[j];
-            if (p & 0x80000000u) {                              // an in-flight session of this key
-                const int64_t q = p & 0x7fffffffu;
-                ss[ns] = a.in.start[q];
-                se[ns] = a.in.end[q];
-                for (int cc = 0; cc < nacc; ++cc) acc(cc, ns) = a.in.acc[(int64_t)cc * a.in.stride + q];
-                ++ns;
-                continue;
-            }
-            const int64_t r = p;
-            const int64_t ts = a.ts[r];
-            const int64_t ws = ts, we = jm::wadd(ts, a.gapc ? a.gapc[r] : a.gap);   // EventTimeSessionWindows.assignWindows :61-63
-            // MergingWindowSet.addWindow: the in-flight sessions intersecting the new window
-            int64_t first = -1, nm = 0, cs = ws, ce = we;
-            bool covers = false;
-            for (int64_t s = 0; s < ns; ++s) {
-                if (!(ss[s] <= we && se[s] >= ws)) continue;    // TimeWindow.intersects
-                ++nm;
-                if (first < 0) first = s;
-                cs = ss[s] < cs ? ss[s] : cs;                   // TimeWindow.cover
-                ce = se[s] > ce ? se[s] : ce;
-                covers = covers || (ss[s] <= ws && se[s] >= we);
-            }
-            int64_t act = first;
-            if (nm > 1 || (nm == 1 && !covers)) {               // MergeFunction.merge (WindowOperator.java:296-349)
-                if (jm::wadd(jm::wsub(ce, 1), a.lateness) <= a.wm) { raise_error(a.st, FWA_E_MERGE_LATE); failed = true; break; }
-                for (int64_t s = ns - 1; s >= 0; --s) {         // mergeNamespaces into the first, drop the rest
-                    if (s == first || !(ss[s] <= we && se[s] >= ws)) continue;
-                    for (int cc = 0; cc < nacc; ++cc)
-                        acc(cc, first) = acc_combine(cc == 0 ? ACC_ADD_I64 : c.acc_kind[cc], acc(cc, first), acc(cc, s));
-                    --ns;
-                    if (s != ns) {
-                        ss[s] = ss[ns]; se[s] = se[ns];
-                        for (int cc = 0; cc < nacc; ++cc) acc(cc, s) = acc(cc, ns);
-                        if (first == ns) first = s;
-                    }
-                }
-                act = first;
-                ss[act] = cs;
-                se[act] = ce;
-            }
-            const int64_t aw_end = act >= 0 ? se[act] : we;
-            if (sess_cleanup(jm::wsub(aw_end, 1), a.lateness) <= a.wm) {   // isWindowLate -> retireWindow, skip
-                if (act >= 0) {
-                    --ns;
-                    if (act != ns) { ss[act] = ss[ns]; se[act] = se[ns]; for (int cc = 0; cc < nacc; ++cc) acc(cc, act) = acc(cc, ns); }
-                }
-                // Table: every skipped record counts (WindowOperator.java:386-389); DataStream: only if
-                // isElementLate (WindowOperator.java:425-433, :597-601)
-                if (table || jm::wadd(ts, a.lateness) <= a.wm) {
-                    ++dropped;
-                    if (a.dropidx) a.dropidx[atomicAdd(&a.st->drop_n, 1ull)] = (int32_t)r;
-                }
-                continue;
-            }
-            if (act < 0) {                                      // new self-contained session
-                act = ns++;
-                ss[act] = ws;
-                se[act] = we;
-                acc(0, act) = 0ull;
-                for (int cc = 1; cc < nacc; ++cc) acc(cc, act) = ident_of(c.acc_kind[cc]);
-            }
-            acc(0, act) += 1ull;                                // windowState.add (AggregateFunction.add)
-            for (int cc = 1; cc < nacc; ++cc)
-                acc(cc, act) = acc_combine(c.acc_kind[cc], acc(cc, act),
-                                           acc_input(c.agg[a.col_owner[cc]], a.cols[c.agg[a.col_owner[cc]].col], r,
-                                                     a.nulls[c.agg[a.col_owner[cc]].col]));
-            if (jm::wsub(se[act], 1) <= a.wm) {                 // EventTimeTrigger.onElement: FIRE at once
-                const unsigned long long row = atomicAdd(a.lr_n, 1ull);
-                if ((int64_t)row >= a.lr_cap) { raise_error(a.st, FWA_E_STATE); continue; }
-                a.lr_key[row] = sess_key_of(a.key_table, a.capacity, kid);
-                a.lr_start[row] = ss[act];
-                a.lr_end[row] = se[act];
-                for (int jj = 0; jj < c.nout; ++jj) {
-                    const AggDesc d = c.agg[jj];
-                    write_agg(d, acc(0, act), d.acc > 0 ? acc(d.acc, act) : 0ull, d.nn > 0 ? acc(d.nn, act) : 0ull,
-                              a.lr_agg[jj], nullptr, (int64_t)row);
-                }
-            }
-        }
-        for (int64_t s = 0; s < ns; ++s) {                      // the key's sessions after the push
-            const int64_t o = ncl + (int64_t)atomicAdd(&a.ctr->n_out_sp, 1ull);
-            a.out.kid[o] = kid;
-            a.out.start[o] = ss[s];
-            a.out.end[o] = se[s];
-            for (int cc = 0; cc < nacc; ++cc) a.out.acc[(int64_t)cc * a.out.stride + o] = acc(cc, s);
-        }
-    }
-    for (int sh = 32; sh >= 1; sh >>= 1) dropped += __shfl_xor(dropped, sh);
-    if ((threadIdx.x & 63) == 0 && dropped) atomicAdd(&a.st->dropped, dropped);
-}
-
-struct Sess2FireArgs {
-    SessList in, out;
-    int64_t n_in;
-    int64_t prev_wm, wm, lateness;
-    const unsigned long long* key_table;
-    int64_t capacity;
-    int64_t* o_key;
-    int64_t* o_start;
-    int64_t* o_end;
-    void* o_agg[FWA_MAX_AGGS];
-    uint8_t* o_null[FWA_MAX_AGGS];
-    int64_t out_cap;
-    SessCtr* ctr;
-    DevStatus* st;
-};
-
-// Watermark advance prev -> wm: emit every session with prev < end - 1 <= wm (EventTimeTrigger.onEventTime
-// / AfterEndOfWindow); keep every session whose cleanup time is still after wm (clearAllState otherwise).
-// A block owns a contiguous chunk of kSessFireItems * kBlock sessions and reserves its emitted rows and kept sessions
-// with one atomic per counter (a per-wave reservation on the two counters serialised ~23 K waves per fire: 0.33 ms on
-// C5s); the flags are computed twice, once to count and once to write.
-constexpr int kSessFireItems = 16;
-__global__ void __launch_bounds__(kBlock) sess2_fire_kernel(Sess2FireArgs f, const EngineConst* __restrict__ cp) {
-    const EngineConst& c = *cp;
-    constexpr int kW = kBlock / 64;
-    __shared__ uint32_t s_wr[kW], s_wk[kW];
-    __shared__ unsigned long long s_base[2];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int64_t c0 = (int64_t)blockIdx.x * kBlock * kSessFireItems;
-    auto flags = [&](int64_t j, int64_t& end, bool& fire, bool& keep) {
-        const bool act = j < f.n_in;
-        end = act ? f.in.end[j] : 0;
-        const int64_t mt = jm::wsub(end, 1);
-        fire = act && mt > f.prev_wm && mt <= f.wm;
-        keep = act && !(sess_cleanup(mt, f.lateness) <= f.wm);
-    };
-    uint32_t nr = 0, nk = 0;
-    for (int it = 0; it < kSessFireItems; ++it) {
-        int64_t end; bool fire, keep;
-        flags(c0 + (int64_t)it * kBlock + threadIdx.x, end, fire, keep);
-        nr += (uint32_t)__popcll(__ballot(fire));
-        nk += (uint32_t)__popcll(__ballot(keep));
-    }
-    if (lane == 0) { s_wr[wv] = nr; s_wk[wv] = nk; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t tr = 0, tk = 0;
-        for (int w = 0; w < kW; ++w) { const uint32_t x = s_wr[w], y = s_wk[w]; s_wr[w] = tr; s_wk[w] = tk; tr += x; tk += y; }
-        s_base[0] = tr ? atomicAdd(&f.st->rows, (unsigned long long)tr) : 0ull;
-        s_base[1] = tk ? atomicAdd(&f.ctr->n_keep, (unsigned long long)tk) : 0ull;
-    }
-    __syncthreads();
-    unsigned long long pr = s_base[0] + s_wr[wv], pk = s_base[1] + s_wk[wv];
-    const unsigned long long lt = (1ull << lane) - 1ull;
-    for (int it = 0; it < kSessFireItems; ++it) {
-        const int64_t j = c0 + (int64_t)it * kBlock + threadIdx.x;
-        int64_t end; bool fire, keep;
-        flags(j, end, fire, keep);
-        const unsigned long long mf = __ballot(fire), mk = __ballot(keep);
-        if (fire) {
-            const unsigned long long row = pr + __popcll(mf & lt);
-            if ((int64_t)row >= f.out_cap) raise_error(f.st, FWA_E_STATE);
-            else {
-                const uint32_t kid = f.in.kid[j];
-                f.o_key[row] = sess_key_of(f.key_table, f.capacity, kid);
-                f.o_start[row] = f.in.start[j];
-                f.o_end[row] = end;
-                const uint64_t cnt = f.in.acc[j];
-                for (int jj = 0; jj < c.nout; ++jj) {
-                    const AggDesc d = c.agg[jj];
-                    write_agg(d, cnt, d.acc > 0 ? f.in.acc[(int64_t)d.acc * f.in.stride + j] : 0ull,
-                              d.nn > 0 ? f.in.acc[(int64_t)d.nn * f.in.stride + j] : 0ull, f.o_agg[jj], f.o_null[jj], (int64_t)row);
-                }
-            }
-        }
-        if (keep) {
-            const unsigned long long k = pk + __popcll(mk & lt);
-            f.out.kid[k] = f.in.kid[j];
-            f.out.start[k] = f.in.start[j];
-            f.out.end[k] = end;
-            for (int cc = 0; cc < c.nacc; ++cc) f.out.acc[(int64_t)cc * f.out.stride + k] = f.in.acc[(int64_t)cc * f.in.stride + j];
-        }
-        pr += __popcll(mf);
-        pk += __popcll(mk);
-    }
-}
+#include "sessions.inc"               // session kernels
 
 // ------------------------------------------------------------------------------------------------
 // utility kernels
@@ -2896,6 +1753,21 @@ enum { kSnapHdr = 32 };                                       // header words
 
 extern "C" {
 
+// host functions used ahead of their definitions
+static int create_engine(const fwa_config* cfg, fwa_engine** out);
+static int push_body(fwa_engine* e, const int64_t* keys, const int64_t* ts, const void* const* val_cols,
+                     const uint8_t* const* null_cols, const int32_t* key_hash, int64_t n, int32_t flags,
+                     int64_t* late_dropped_out);
+static int push_settle(fwa_engine* e, IngestArgs& a, int64_t n, bool ran_v2, bool status_enqueued,
+                       int64_t* late_dropped_out);
+static int push_session(fwa_engine* e, IngestArgs& a, int64_t* dropped_out);          // sessions_host.inc
+static int fire_sessions(fwa_engine* e, int64_t wm, int64_t* nrows);                  // sessions_host.inc
+static int upload_windows(fwa_engine* e, const std::vector<FireWindow>& hw, const std::vector<int32_t>& hs);
+static int emit_late_rows(fwa_engine* e);
+static int finish_afire(fwa_engine* e);
+static int retire_slices(fwa_engine* e, int64_t wm);
+static int fill_out(fwa_engine* e, int64_t nrows, fwa_out* out);
+
 const char* fwa_version(void) { return "flink_amd 0.1 (gfx950)"; }
 
 // (a NULL handle: why this thread's last fwa_create refused its configuration, where it gave a reason)
@@ -2966,8 +1838,6 @@ void fwa_destroy(fwa_engine* e) {
     if (e->stream) (void)hipStreamDestroy(e->stream);
     delete e;
 }
-
-static int create_engine(const fwa_config* cfg, fwa_engine** out);
 
 int fwa_create(const fwa_config* ucfg, fwa_engine** out) {
     if (!ucfg || !out) return FWA_E_ARG;
@@ -3376,749 +2246,7 @@ static int account_ingest(fwa_engine* e) {  // after the stream was synchronised
     return FWA_OK;
 }
 
-static int ensure_v2_buffers(fwa_engine* e, int64_t n, bool need_bn) {
-    const int64_t per = n / ((int64_t)e->np * kSub);                 // expected records per sub-bucket
-    const int64_t capb = per + per / 4 + 2048;
-    if (capb > e->capb) {
-        for (void* p : {(void*)e->d_bkey, (void*)e->d_brel, (void*)e->d_bn, (void*)e->d_bval[0], (void*)e->d_bval[1]}) if (p) HIPCHK(e, hipFree(p));
-        e->d_bkey = nullptr;
-        e->d_brel = nullptr;
-        e->d_bn = nullptr;
-        e->d_bval[0] = e->d_bval[1] = nullptr;
-        const int64_t ent = capb * e->np * kSub + 8 * kMaxPart;  // + a trash area (partition3's masked stores)
-        HIPCHK(e, hipMalloc(&e->d_bkey, (e->nv == 1 ? 12 : 8) * ent));   // 12: narrow {key, value, slice} entries
-        HIPCHK(e, hipMalloc(&e->d_brel, 2 * ent));
-        for (int v = 0; v < e->nv; ++v) HIPCHK(e, hipMalloc(&e->d_bval[v], 8 * ent));
-        e->capb = capb;
-    }
-    if (need_bn && !e->d_bn) HIPCHK(e, hipMalloc(&e->d_bn, 2 * (e->capb * e->np * kSub + 8 * kMaxPart)));
-    if (!e->d_bcnt) {
-        HIPCHK(e, hipMalloc(&e->d_bcnt, sizeof(uint32_t) * kMaxPart * kSub));
-        HIPCHK(e, hipMalloc(&e->d_rel2slot, (sizeof(int32_t) + 2) * kRelCap));   // rel2slot | relcode | relfresh
-    }
-    return FWA_OK;
-}
-
-// FWA_OPT_PROFILE: wait for a profiled kernel (events a, b) and print its per-block phase cycle counters (average
-// over the nb blocks and the slowest block): Phase P marks 6 phases, Phase A 8.
-static int print_phase_profile(fwa_engine* e, const char* tag, hipEvent_t a, hipEvent_t b, int nb, int nph) {
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    float ms = 0.f;
-    HIPCHK(e, hipEventElapsedTime(&ms, a, b));
-    std::vector<long long> hp(8 * (size_t)nb);
-    HIPCHK(e, hipMemcpy(hp.data(), e->d_prof, sizeof(long long) * 8 * nb, hipMemcpyDeviceToHost));
-    double tot[8] = {0};
-    int bmax = 0;
-    long long bsum_max = -1;
-    for (int blk = 0; blk < nb; ++blk) {
-        long long bs = 0;
-        for (int k = 0; k < nph; ++k) { tot[k] += (double)hp[blk * 8 + k] / nb; bs += hp[blk * 8 + k]; }
-        if (bs > bsum_max) { bsum_max = bs; bmax = blk; }
-    }
-    fprintf(stderr, "[%s] kernel %.3f ms; per-block avg cycles:", tag, ms);
-    for (int k = 0; k < nph; ++k) fprintf(stderr, " %.0f", tot[k]);
-    fprintf(stderr, " | slowest block %d:", bmax);
-    for (int k = 0; k < nph; ++k) fprintf(stderr, " %lld", hp[bmax * 8 + k]);
-    fprintf(stderr, "\n");
-    return FWA_OK;
-}
-
-// Two-phase ingest. Sets *ran = false (and leaves no state change besides key insertions) when the
-// batch must take the v1 path instead (bucket overflow on skewed keys).
-static int ensure_sort_tmp(fwa_engine* e, size_t bytes);
-static int push_v2(fwa_engine* e, IngestArgs& a, bool* ran) {
-    *ran = false;
-    // combiner accumulator layout (compile-time in combine3) and the skew mode (PRE, partition3)
-    int layout = 0;
-    if (e->nacc_comb == 1) layout = 2;
-    else if (e->nacc_comb == 2 && e->ec.acc_kind[1] == ACC_ADD_I64) {
-        for (int j = 0; j < e->cfg.num_aggs; ++j)
-            if (e->ec.agg[j].acc == 1 && e->ec.agg[j].vslot == 0) layout = 1;
-    }
-    const bool pre_ok = (layout == 2 && e->nv == 0) || (layout == 1 && e->nv == 1 && e->vsize[0] == 8);
-    // partial accumulators (fwa_push_partials): the PRE buckets carry each row's record count, the value
-    // column is the partial BIGINT sum; other aggregate lists keep the v1 path
-    if (a.pcount && (!pre_ok || e->cfg.nullable_cols || e->opt_partials_v1)) return FWA_OK;
-    const bool pre = a.pcount || (pre_ok && e->opt_pre != 0 && (e->opt_pre == 1 || e->pre));
-    int rc = ensure_v2_buffers(e, a.n, pre);
-    if (rc) return rc;
-    const int64_t q_base = e->live.empty() ? 0 : e->live.begin()->first;
-    // rel2slot (combine) and relcode (partition): the directory restricted to [q_base, q_base + kRelCap)
-    // with each slice's acceptance under the current watermark (WindowOperator.isWindowLate /
-    // SlicingWindowOperator lateness, as in ingest_kernel)
-    std::vector<int32_t> r2s(kRelCap + kRelCap / 2, -1);
-    uint8_t* code = (uint8_t*)(r2s.data() + kRelCap);
-    memset(code, kCodeSlow, kRelCap);
-    // slots no record reached yet hold their identities: the combiner's merge of such a slice stores without reading
-    uint8_t* fresh = code + kRelCap;
-    memset(fresh, 0, kRelCap);
-    int64_t rel_hi = -1;                              // (rel_lo = 0: q_base is the first live slice)
-    const bool mp = e->opt_mp == 1 || (e->opt_mp != 0 && e->mp);   // combiner window passes (slices smaller than chunks)
-    // stale slots under the slices of this push: the combiner overwrites them (fresh 2) when it
-    // merges every slice of its window once and no other kernel writes slots first; otherwise they are reset here. Live
-    // slices past the tables reach their slots through the v1 replay only: reset too.
-    const bool lazy = !pre && !mp && !(e->opt_variant & (512 | 1));
-    e->push_stale.clear();
-    for (auto& kv : e->live) {
-        const int64_t rel = kv.first - q_base;
-        if (e->n_stale && e->stale[kv.second] && (!lazy || rel < 0 || rel >= kRelCap || e->touched[kv.second])) {
-            e->stale[kv.second] = 0;
-            e->n_stale--;
-            e->pending_reset.push_back(kv.second);
-        }
-        if (rel < 0 || rel >= kRelCap) continue;
-        rel_hi = rel;
-        r2s[rel] = kv.second;
-        fresh[rel] = (e->touched[kv.second] || (e->opt_variant & 1)) ? 0 : 1;   // variant bit 0: A/B without
-        if (e->n_stale && e->stale[kv.second]) {
-            fresh[rel] = 2;
-            e->push_stale.push_back({kv.first, kv.second});
-        }
-        int64_t thr;
-        bool always;
-        accept_threshold(e, kv.first, &thr, &always);
-        if (!always && !(a.wm < thr)) code[rel] = kCodeDrop;
-        else if (e->lateness > 0 && a.wm >= trig(e, jm::wsub(first_window_end(e, kv.first), 1))) code[rel] = kCodeSlow;
-        else code[rel] = kCodeAccept;
-    }
-    if ((rc = flush_resets(e))) return rc;
-    if (rel_hi < kRelTabN && !(e->opt_variant & 256)) {   // a narrow span: the tables by value (variant bit 8: A/B)
-        RelTab tab;
-        memset(&tab, 0, sizeof(tab));
-        tab.n = (int32_t)(rel_hi + 1);
-        for (int32_t j = 0; j < tab.n; ++j) { tab.slot[j] = r2s[j]; tab.code[j] = code[j]; tab.fresh[j] = fresh[j]; }
-        rc = reset_push_status(e, true, &tab);
-    } else {
-        rc = upload(e, e->d_rel2slot, r2s.data(), (sizeof(int32_t) + 2) * kRelCap);
-        if (rc) return rc;
-        rc = reset_push_status(e, true);
-    }
-    if (rc) return rc;
-    PartArgs pa;
-    memset(&pa, 0, sizeof(pa));
-    pa.keys = a.keys;
-    pa.ts = a.ts;
-    for (int c = 0; c < FWA_MAX_COLS; ++c) pa.cols[c] = a.cols[c];
-    if (a.pcount) {                   // partial rows: cols[] is indexed by aggregate; the carried value is the
-        pa.pcount = a.pcount;         // accumulator column of the BIGINT sum (layout 1)
-        for (int j = 0; j < e->cfg.num_aggs; ++j)
-            if (e->ec.agg[j].acc == 1 && layout == 1) pa.cols[e->vcol[0]] = a.cols[j];
-    }
-    pa.key_hash = a.key_hash;
-    pa.n = a.n;
-    pa.wm = a.wm;
-    pa.relcode = (const uint8_t*)(e->d_rel2slot + kRelCap);
-    pa.rel2slot = e->d_rel2slot;
-    pa.touched = e->d_touched;
-    pa.epoch = std::max<int32_t>(1, e->push_epoch);
-    pa.spill = e->d_spill;
-    pa.q_base = q_base;
-    pa.fast_m = 0;
-    pa.fast_lim = 0;
-    pa.base_ts = 0;
-    pa.fast_sh = 0;
-    if (!e->cfg.tz_n && e->g > 0 && (uint64_t)e->g * kRelCap < (1ull << 32) && q_base > -(1ll << 40) && q_base < (1ll << 40)) {
-        // floor(n / g) = (n * ceil(2^(32+L) / g)) >> (32+L) for every n < 2^32, L = ceil(log2 g) (round-up method;
-        // the magic has at most 33 bits, so n * m fits 64 bits)
-        int L = 0;
-        while ((1ull << L) < (uint64_t)e->g) ++L;
-        const __int128 b = (__int128)e->off + (__int128)q_base * e->g;
-        if (b > (__int128)INT64_MIN / 2 && b < (__int128)INT64_MAX / 2) {
-            pa.fast_sh = 32 + L;
-            pa.fast_m = ((1ull << (32 + L)) + (uint64_t)e->g - 1) / (uint64_t)e->g;
-            pa.fast_lim = (uint64_t)e->g * kRelCap;
-            pa.base_ts = (int64_t)b;
-        }
-    }
-    pa.b_key = e->d_bkey;
-    pa.b_rel = e->d_brel;
-    pa.b_n = pre ? e->d_bn : nullptr;
-    pa.key_table = e->d_keys;
-    pa.key_mask = (uint64_t)e->capacity - 1;
-    pa.seg_log = e->seg_log;
-    pa.slot_base = e->d_slot_base;
-    pa.stride = e->stride;
-    pa.b_val0 = e->d_bval[0];
-    pa.b_val1 = e->d_bval[1];
-    pa.b_cnt = e->d_bcnt;
-    pa.capb = e->capb;
-    pa.trash = (uint64_t)e->capb * e->np * kSub;
-    pa.spill_cap = e->spill_cap;
-    pa.part_bits = e->part_bits;
-    pa.np = e->np;
-    pa.sub_major = (e->opt_variant & 4) ? 0 : 1;   // variant bit 2: partition-major buckets (A/B)
-    pa.iota1 = e->ec.red_iota && e->nv == 2 && e->vcol[1] == kIotaCol && e->vsize[1] == 4 && !(e->opt_variant & 16);
-    if (e->iota_pending && !pa.iota1) { int rc = ensure_iota(e); if (rc) return rc; }
-    for (int v = 0; v < 2; ++v) { pa.vcol[v] = e->vcol[v]; pa.vsize[v] = e->vsize[v]; }
-    pa.dropidx = a.pcount ? nullptr : a.dropidx;   // partial rows: no record indices (as in v1)
-    for (int c = 0; c < FWA_MAX_COLS; ++c) { pa.nulls[c] = a.nulls[c]; pa.any_null |= a.nulls[c] != nullptr; }
-    pa.st = e->d_st;
-    if (e->opt_profile && !e->d_prof) HIPCHK(e, hipMalloc(&e->d_prof, sizeof(long long) * 8 * kMaxPart));
-    pa.prof = e->opt_profile ? e->d_prof : nullptr;
-    HIPCHK(e, hipEventRecord(e->ev[4], e->stream));
-    const int threads = 1024;
-    const int items = e->nv == 2 ? 4 : (e->nv == 1 ? 6 : 8);
-    const int64_t tile = (int64_t)items * threads;
-    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((a.n + tile - 1) / tile, 256));
-    const int vw = (e->vsize[0] == 8 ? 1 : 0) | (e->vsize[1] == 8 ? 2 : 0);
-    // ownership is checked per record unless the handle owns every key group; dictionary ids always (their key group
-    // may be past max_parallelism: key group -1, rejected with FWA_E_KEYGROUP)
-    const bool kg_all = e->cfg.kg_start == 0 && e->cfg.kg_end == e->cfg.max_parallelism - 1 &&
-                        e->cfg.key_kind != FWA_KEY_GROUP_PREFIXED;
-    const int kgm = kg_all ? 0 : (e->cfg.key_kind == FWA_KEY_PREHASHED ? 2 : 1);
-    auto al16 = [](const void* q) { return q == nullptr || ((uintptr_t)q & 15) == 0; };
-    const bool w16 = kgm == 0 && al16(pa.keys) && al16(pa.ts) &&
-                     (e->nv == 0 || ((uintptr_t)pa.cols[pa.vcol[0]] & ((e->vsize[0] == 8) ? 15 : 7)) == 0);
-    // narrow bucket entries (partition3 / combine3 NW): COUNT + one BIGINT SUM over an 8-byte column, the paired-load
-    // kernel; on by default until a push finds more than 1/64 of its records needing 64-bit keys or values
-    const bool narrow = e->opt_narrow != 0 && (e->opt_narrow == 1 || e->narrow) && layout == 1 && e->nv == 1 &&
-                        (vw & 1) && w16 && !pre && !a.pcount;
-    // ... and for an 8-byte value column beside a 4-byte one (C5: DOUBLE and FLOAT): key and FLOAT bits share a word
-    const bool narrow2 = e->opt_narrow != 0 && (e->opt_narrow == 1 || e->narrow) && layout == 0 && e->nv == 2 && vw == 1 &&
-                         kgm == 0 && !pre && !a.pcount;
-    e->narrow_used = narrow || narrow2;
-    const bool roll = !(e->opt_variant & 1024);
-#define P3LAUNCH(NV, IT, VW) do { \
-        if (kgm == 0) partition3_kernel<NV, IT, 1024, VW, 0><<<grid, 1024, 0, e->stream>>>(pa, e->d_ec); \
-        else if (kgm == 1) partition3_kernel<NV, IT, 1024, VW, 1><<<grid, 1024, 0, e->stream>>>(pa, e->d_ec); \
-        else partition3_kernel<NV, IT - 2, 1024, VW, 2><<<grid, 1024, 0, e->stream>>>(pa, e->d_ec); } while (0)
-    // (supplied key hashes: one column more per tile, two items fewer per lane keep the kernel free of VGPR spills)
-#define PRELAUNCH(NV) do { const int gp = (int)std::max<int64_t>(1, std::min<int64_t>((a.n + 4095) / 4096, 256)); \
-        if (kgm == 0) partition3_kernel<NV, 4, 1024, 3, 0, 1><<<gp, 1024, 0, e->stream>>>(pa, e->d_ec); \
-        else if (kgm == 1) partition3_kernel<NV, 4, 1024, 3, 1, 1><<<gp, 1024, 0, e->stream>>>(pa, e->d_ec); \
-        else partition3_kernel<NV, 4, 1024, 3, 2, 1><<<gp, 1024, 0, e->stream>>>(pa, e->d_ec); } while (0)
-    if (pre) { if (e->nv == 0) PRELAUNCH(0); else PRELAUNCH(1); }
-    else if (e->nv == 0) P3LAUNCH(0, 8, 3);
-    // rolling issue of the next tile's loads (partition3 ROLL); FWA_OPT_INGEST_VARIANT bit 10: in one burst behind the
-    // scan instead (A/B)
-    else if (narrow && roll) partition3_kernel<1, 6, 1024, 3, 0, 0, 1, 1, 1><<<grid, 1024, 0, e->stream>>>(pa, e->d_ec);
-    else if (narrow) partition3_kernel<1, 6, 1024, 3, 0, 0, 1, 1><<<grid, 1024, 0, e->stream>>>(pa, e->d_ec);
-    else if (narrow2) partition3_kernel<2, 4, 1024, 1, 0, 0, 0, 2><<<grid, 1024, 0, e->stream>>>(pa, e->d_ec);
-    else if (e->nv == 1 && w16 && (vw & 1)) partition3_kernel<1, 6, 1024, 3, 0, 0, 1><<<grid, 1024, 0, e->stream>>>(pa, e->d_ec);
-    else if (e->nv == 1 && w16) partition3_kernel<1, 6, 1024, 2, 0, 0, 1><<<grid, 1024, 0, e->stream>>>(pa, e->d_ec);
-    else if (e->nv == 1) { if (vw & 1) P3LAUNCH(1, 6, 3); else P3LAUNCH(1, 6, 2); }
-    else if (vw == 3) P3LAUNCH(2, 4, 3); else if (vw == 2) P3LAUNCH(2, 4, 2);
-    else if (vw == 1) P3LAUNCH(2, 4, 1); else P3LAUNCH(2, 4, 0);
-#undef P3LAUNCH
-#undef PRELAUNCH
-    HIPCHK(e, hipGetLastError());
-    HIPCHK(e, hipEventRecord(e->ev[5], e->stream));
-    if (e->opt_profile) {
-        int rc2 = print_phase_profile(e, "pprof", e->ev[4], e->ev[5], grid, 6);
-        if (rc2) return rc2;
-    }
-    // no host round trip between the phases: Phase P marks touched slots itself, spills bucket
-    // overflow to the v1 replay list, and the combiner applies stragglers in place
-    CombineArgs ca;
-    memset(&ca, 0, sizeof(ca));
-    ca.b_key = e->d_bkey;
-    ca.b_rel = e->d_brel;
-    ca.b_n = pre ? e->d_bn : nullptr;
-    ca.key_table = e->d_keys;
-    ca.b_val0 = e->d_bval[0];
-    ca.b_val1 = e->d_bval[1];
-    ca.b_cnt = e->d_bcnt;
-    ca.capb = e->capb;
-    ca.seg_log = e->seg_log;
-    ca.np = e->np;
-    ca.sl = e->sl;
-    ca.sub_major = pa.sub_major;
-    ca.rel2slot = e->d_rel2slot;
-    // (not with PRE buckets: Phase P applies merged entries past a full sub-bucket to the slots with device atomics
-    // before this merge -- tests/test_skew_gpu.py::test_pre_entries_past_bucket_end_applied_with_atomics)
-    ca.relfresh = pre ? nullptr : (const uint8_t*)(e->d_rel2slot + kRelCap) + kRelCap;
-    ca.stale = e->push_stale.empty() ? 0 : 1;
-    ca.q_base = q_base;
-    ca.slot_base = e->d_slot_base;
-    ca.stride = e->stride;
-    ca.st = e->d_st;
-    ca.prof = pa.prof;
-    HIPCHK(e, hipEventRecord(e->ev[6], e->stream));
-    const size_t seg3 = (size_t)1 << e->seg_log;
-    const size_t lds3 = seg3 * 8 + 2 * seg3 * 4 + (size_t)(e->nacc_comb - 1) * 2 * seg3 * 8 + 4 * 4 * kSub + 16;
-    // entries per lane and chunk: the largest counts whose kernels keep every value in registers at 1024 threads (a VGPR
-    // spill is not harmless here, DESIGN.md section 4 "Skewed keys"; tests/test_abi.py checks the code object): 4, 3 with
-    // two carried value columns, 6 for narrow entries (the lean body too: 8 spill), 2 with window passes. 512-thread blocks with twice the entries are
-    // spill-free too but slower (r05 A/B, profiles/r05_combine_geometry_ab.txt). -D switches for A/B builds only.
-#ifndef FWA_C3_TH
-#define FWA_C3_TH 1024
-#endif
-#ifndef FWA_C3_IT0
-#define FWA_C3_IT0 4
-#endif
-#ifndef FWA_C3_IT1
-#define FWA_C3_IT1 4
-#endif
-#ifndef FWA_C3_IT2
-#define FWA_C3_IT2 3
-#endif
-#ifndef FWA_C3_NIT
-#define FWA_C3_NIT 6
-#endif
-#ifndef FWA_MP_IT
-#define FWA_MP_IT 2
-#endif
-    constexpr int TH3 = FWA_C3_TH;
-#define C3M(IT, NV, LY, PR) do { if (mp) combine3_kernel<FWA_MP_IT, 2, NV, TH3, LY, PR, 1><<<e->np, TH3, lds3, e->stream>>>(ca, e->d_ec); \
-        else combine3_kernel<IT, 2, NV, TH3, LY, PR, 0><<<e->np, TH3, lds3, e->stream>>>(ca, e->d_ec); } while (0)
-#define C3L(IT, NV) do { \
-        if (pre && layout == 1) C3M(IT, 1, 1, 1); \
-        else if (pre) C3M(IT, 0, 2, 1); \
-        else if (layout == 1) C3M(IT, NV, 1, 0); \
-        else if (layout == 2) C3M(IT, NV, 2, 0); \
-        else C3M(IT, NV, 0, 0); } while (0)
-    if (narrow) {   // packed entries free the prefetch registers: more entries per lane and chunk
-        if (mp) combine3_kernel<FWA_MP_IT, 2, 1, TH3, 1, 0, 1, 1><<<e->np, TH3, lds3, e->stream>>>(ca, e->d_ec);
-        // the lean body (ingest.inc: 4-byte key image in LDS, first probes in batches of 3, misses deferred); variant
-        // bit 1: the general body on the same entries (A/B)
-        else if (TH3 != 1024 || (e->opt_variant & 2)) combine3_kernel<FWA_C3_NIT, 2, 1, TH3, 1, 0, 0, 1><<<e->np, TH3, lds3, e->stream>>>(ca, e->d_ec);
-        else combine3_kernel<6, 2, 1, 1024, 1, 0, 0, 1, 3><<<e->np, 1024, lds3, e->stream>>>(ca, e->d_ec);
-    } else if (narrow2) {
-        if (mp) combine3_kernel<FWA_MP_IT, 2, 2, TH3, 0, 0, 1, 2><<<e->np, TH3, lds3, e->stream>>>(ca, e->d_ec);
-        else combine3_kernel<4, 2, 2, TH3, 0, 0, 0, 2><<<e->np, TH3, lds3, e->stream>>>(ca, e->d_ec);
-    } else if (e->nv == 0) C3L(FWA_C3_IT0, 0);
-    else if (e->nv == 1) C3L(FWA_C3_IT1, 1);
-    else C3L(FWA_C3_IT2, 2);
-#undef C3L
-#undef C3M
-    HIPCHK(e, hipGetLastError());
-    HIPCHK(e, hipEventRecord(e->ev[7], e->stream));
-    e->v2_timing_pending = true;
-    if (e->opt_profile) {
-        int rc2 = print_phase_profile(e, "aprof", e->ev[6], e->ev[7], e->np, 8);
-        if (rc2) return rc2;
-    }
-    e->ingest_launches++;
-    e->ingest_records += a.n;
-    *ran = true;
-    return FWA_OK;
-}
-
-// Sessions: classify -> route -> bulk gap-scan (sort by (kid, start), segmented max-scan,
-// cluster ids, wave-segmented reduction) and the arrival-order walk for keys with order-sensitive records.
-struct KidEq {                       // equal kid part of a (kid << tb | start - base) sort key
-    int tb;
-    __host__ __device__ bool operator()(unsigned long long x, unsigned long long y) const { return (x >> tb) == (y >> tb); }
-};
-struct MaxI64 {
-    __host__ __device__ int64_t operator()(int64_t x, int64_t y) const { return x > y ? x : y; }
-};
-
-static int ensure_sort_tmp(fwa_engine* e, size_t bytes) {
-    if (bytes <= e->sort_tmp_bytes) return FWA_OK;
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    if (e->d_sort_tmp) HIPCHK(e, hipFree(e->d_sort_tmp));
-    e->d_sort_tmp = nullptr;
-    HIPCHK(e, hipMalloc(&e->d_sort_tmp, bytes + bytes / 4));
-    e->sort_tmp_bytes = bytes + bytes / 4;
-    return FWA_OK;
-}
-
-static int ensure_sess_lists(fwa_engine* e, int64_t need) {
-    if (need <= e->ss_cap) return FWA_OK;
-    const int64_t cap = std::max<int64_t>(need + need / 4, 1 << 12);
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    for (int q = 0; q < 2; ++q) {
-        SessList nl;
-        nl.stride = cap;
-        HIPCHK(e, hipMalloc(&nl.kid, 4 * (size_t)cap));
-        HIPCHK(e, hipMalloc(&nl.start, 8 * (size_t)cap));
-        HIPCHK(e, hipMalloc(&nl.end, 8 * (size_t)cap));
-        HIPCHK(e, hipMalloc(&nl.acc, 8 * (size_t)cap * e->nacc));
-        SessList& ol = e->ss[q];
-        if (q == e->ss_cur && e->n_ss > 0) {             // keep the live sessions
-            const size_t n = (size_t)e->n_ss;
-            HIPCHK(e, hipMemcpy(nl.kid, ol.kid, 4 * n, hipMemcpyDeviceToDevice));
-            HIPCHK(e, hipMemcpy(nl.start, ol.start, 8 * n, hipMemcpyDeviceToDevice));
-            HIPCHK(e, hipMemcpy(nl.end, ol.end, 8 * n, hipMemcpyDeviceToDevice));
-            for (int cc = 0; cc < e->nacc; ++cc)
-                HIPCHK(e, hipMemcpy(nl.acc + (size_t)cc * cap, ol.acc + (size_t)cc * ol.stride, 8 * n, hipMemcpyDeviceToDevice));
-        }
-        for (void* p : {(void*)ol.kid, (void*)ol.start, (void*)ol.end, (void*)ol.acc}) if (p) HIPCHK(e, hipFree(p));
-        ol = nl;
-    }
-    e->ss_cap = cap;
-    return FWA_OK;
-}
-
-static int ensure_late_rows(fwa_engine* e, int64_t need);
-static int emit_late_rows(fwa_engine* e);
-
-static int read_sess_ctr(fwa_engine* e) {
-    HIPCHK(e, hipMemcpyAsync(e->h_sctr, e->d_sctr, sizeof(SessCtr), hipMemcpyDeviceToHost, e->stream));
-    return sync_status(e);
-}
-
-// Staging buffers, the segment walk (sess2_segment_kernel, or sess3_segment_kernel over cell keys), the scan of the
-// per-wave counts and the compaction into s.out.
-static int launch_segments(fwa_engine* e, Sess2Args& s, int64_t nb, bool cells) {
-    const int64_t nw = (nb + 63) / 64;
-    if (nb > e->sg_cap || nw + 1 > e->sgw_cap) {
-        HIPCHK(e, hipStreamSynchronize(e->stream));
-        if (e->d_sg) HIPCHK(e, hipFree(e->d_sg));
-        e->d_sg = nullptr;
-        e->sg_cap = std::max<int64_t>(nb + nb / 4, 1 << 14);
-        e->sgw_cap = (e->sg_cap + 63) / 64 + 1;
-        const size_t bytes = (size_t)e->sg_cap * (4 + 8 + 8 + 8 * (size_t)e->nacc) + (size_t)e->sgw_cap * (4 + 4 + 8) + 1024;
-        HIPCHK(e, hipMalloc(&e->d_sg, bytes));
-    }
-    char* sp = (char*)e->d_sg;
-    s.sg_start = (int64_t*)sp; sp += 8 * (size_t)e->sg_cap;
-    s.sg_end = (int64_t*)sp; sp += 8 * (size_t)e->sg_cap;
-    s.sg_acc = (unsigned long long*)sp; sp += 8 * (size_t)e->sg_cap * e->nacc;
-    s.sg_h0 = (int64_t*)sp; sp += 8 * (size_t)e->sgw_cap;
-    s.sg_kid = (uint32_t*)sp; sp += 4 * (size_t)e->sg_cap;
-    s.sg_cnt = (uint32_t*)sp; sp += 4 * (size_t)e->sgw_cap;
-    s.sg_off = (uint32_t*)sp;
-    s.sg_cap = e->sg_cap;
-    const unsigned sg = (unsigned)std::max<int64_t>(1, std::min<int64_t>((nb + 255) / 256, 1 << 16));
-    switch (e->nacc) {
-        case 1: if (cells) sess3_segment_kernel<1><<<sg, kBlock, 0, e->stream>>>(s, e->d_ec); else sess2_segment_kernel<1><<<sg, kBlock, 0, e->stream>>>(s, e->d_ec); break;
-        case 2: if (cells) sess3_segment_kernel<2><<<sg, kBlock, 0, e->stream>>>(s, e->d_ec); else sess2_segment_kernel<2><<<sg, kBlock, 0, e->stream>>>(s, e->d_ec); break;
-        case 3: if (cells) sess3_segment_kernel<3><<<sg, kBlock, 0, e->stream>>>(s, e->d_ec); else sess2_segment_kernel<3><<<sg, kBlock, 0, e->stream>>>(s, e->d_ec); break;
-        case 4: if (cells) sess3_segment_kernel<4><<<sg, kBlock, 0, e->stream>>>(s, e->d_ec); else sess2_segment_kernel<4><<<sg, kBlock, 0, e->stream>>>(s, e->d_ec); break;
-        default: if (cells) sess3_segment_kernel<5><<<sg, kBlock, 0, e->stream>>>(s, e->d_ec); else sess2_segment_kernel<5><<<sg, kBlock, 0, e->stream>>>(s, e->d_ec); break;
-    }
-    HIPCHK(e, hipGetLastError());
-    HIPCHK(e, hipMemsetAsync(s.sg_cnt + nw, 0, 4, e->stream));
-    size_t bytes = 0;
-    HIPCHK(e, hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, s.sg_cnt, s.sg_off, (int)(nw + 1), e->stream));
-    int rc = ensure_sort_tmp(e, bytes);
-    if (rc) return rc;
-    bytes = e->sort_tmp_bytes;
-    HIPCHK(e, hipcub::DeviceScan::ExclusiveSum(e->d_sort_tmp, bytes, s.sg_cnt, s.sg_off, (int)(nw + 1), e->stream));
-    sess2_compact_kernel<<<1024, kBlock, 0, e->stream>>>(s, nw, e->nacc);
-    HIPCHK(e, hipGetLastError());
-    return FWA_OK;
-}
-
-#include "sessions4_host.inc"
-
-static int push_session(fwa_engine* e, IngestArgs& a, int64_t* dropped_out) {
-    const int64_t n = a.n;
-    const int64_t n_in = e->n_ss;
-    int rc = FWA_OK;
-    if (n + n_in > e->sb_cap) {                           // sort / scan buffers for every element of the push
-        HIPCHK(e, hipStreamSynchronize(e->stream));
-        const int64_t cap = std::max<int64_t>((n + n_in) + (n + n_in) / 4, 1 << 14);
-        auto re = [&](void** p, size_t elem) -> int {
-            if (*p) HIPCHK(e, hipFree(*p));
-            *p = nullptr;
-            HIPCHK(e, hipMalloc(p, elem * (size_t)cap));
-            return FWA_OK;
-        };
-        for (int q = 0; q < 4; ++q) {
-            if ((rc = re((void**)&e->d_skey[q], 8))) return rc;
-            if ((rc = re((void**)&e->d_sval[q], 4))) return rc;
-        }
-        if ((rc = re((void**)&e->d_send2, 8)) || (rc = re((void**)&e->d_smax, 8)) || (rc = re((void**)&e->d_scid, 4)) ||
-            (rc = re((void**)&e->d_rkid, 4)) || (rc = re((void**)&e->d_spk, 8 * (size_t)e->nacc)) || (rc = re((void**)&e->d_spe, 8)))
-            return rc;
-        e->sb_cap = cap;
-    }
-    if ((rc = ensure_sess_lists(e, n_in + n))) return rc;
-    SessCtr z;
-    memset(&z, 0, sizeof(z));
-    z.ts_min = ~0ull;
-    if ((rc = upload(e, e->d_sctr, &z, sizeof(z)))) return rc;
-    HIPCHK(e, hipMemsetAsync(e->d_kflag, 0, (size_t)e->capacity + 1, e->stream));
-    if ((rc = reset_push_status(e))) return rc;
-
-    Sess2Args s;
-    memset(&s, 0, sizeof(s));
-    s.keys = a.keys;
-    s.ts = a.ts;
-    if (!e->tz.empty() && n > 0) {                        // Table GROUP BY SESSION over a TIMESTAMP_LTZ rowtime:
-        if (n > e->lts_cap) {                             // sessions are formed on local wall-clock time
-            if (e->d_lts) HIPCHK(e, hipFree(e->d_lts));
-            e->d_lts = nullptr;
-            HIPCHK(e, hipMalloc(&e->d_lts, 8 * (size_t)n));
-            e->lts_cap = n;
-        }
-        to_local_kernel<<<grid_for(n), kBlock, 0, e->stream>>>(a.ts, e->d_lts, n, e->d_ec);
-        HIPCHK(e, hipGetLastError());
-        s.ts = e->d_lts;
-    }
-    for (int c = 0; c < FWA_MAX_COLS; ++c) s.cols[c] = a.cols[c];
-    s.key_hash = a.key_hash;
-    s.gapc = (e->cfg.flags & FWA_CFG_DYNAMIC_GAP) ? (const int64_t*)a.cols[e->cfg.gap_col] : nullptr;
-    s.n = n;
-    s.wm = local_wm(e, e->wm);
-    s.gap = e->cfg.gap_ms;
-    s.lateness = e->lateness;
-    s.key_table = e->d_keys;
-    s.key_mask = (uint64_t)e->capacity - 1;
-    s.seg_log = e->seg_log;
-    s.part_bits = e->part_bits;
-    s.capacity = e->capacity;
-    s.rkid = e->d_rkid;
-    s.kflag = e->d_kflag;
-    s.in = e->ss[e->ss_cur];
-    s.n_in = n_in;
-    s.out = e->ss[e->ss_cur ^ 1];
-    for (int cc = 0; cc <= kMaxAggsInt; ++cc) s.col_owner[cc] = -1;
-    for (int j = 0; j < e->ec.naggs; ++j)
-        if (e->ec.agg[j].acc > 0 && !e->ec.agg[j].alias) s.col_owner[e->ec.agg[j].acc] = j;
-    for (int col = 0; col < FWA_MAX_COLS; ++col) s.nulls[col] = a.nulls[col];
-    s.ctr = e->d_sctr;
-    s.dropidx = a.dropidx;
-    s.st = e->d_st;
-    // cell path (sess3_*): fixed gap, 32-bit cell keys; redone on the general path below when a record is not
-    // order-free or a start falls outside the cell range (then not tried again for 8 pushes)
-    const int cb = 32 - e->kid_bits;
-    // cell pre-aggregation (sessions4.inc) first; cells or sessions out of its range: the sort-based cell path
-    bool s4_general = false;
-    if (e->opt_cells != 0 && !s.gapc && e->nacc <= 5 && n > 0 && e->cell_skip <= 0 && n + n_in < ((int64_t)1 << 31) &&
-        e->cfg.gap_ms > 0 && e->cfg.gap_ms <= ((int64_t)1 << 27) && e->capacity < ((int64_t)1 << 27) &&
-        (e->capacity + 1 + kS4Kids - 1) / kS4Kids <= 24576) {
-        int verdict = 1;
-        if ((rc = push_session_s4(e, s, n, n_in, dropped_out, &verdict))) return rc;
-        if (verdict == 0) { e->sess_path = 2; return FWA_OK; }
-        s4_general = verdict == 2;
-        memset(&z, 0, sizeof(z));
-        z.ts_min = ~0ull;
-        if ((rc = upload(e, e->d_sctr, &z, sizeof(z)))) return rc;
-        if ((rc = reset_push_status(e))) return rc;
-    }
-    bool tried3 = false;
-    if (e->opt_cells != 0 && !s4_general && !s.gapc && cb >= 1 && e->nacc <= 5 && n > 0 && e->cell_skip <= 0 &&
-        n + n_in < ((int64_t)1 << 31)) {
-        tried3 = true;
-        Sess2Args t = s;
-        t.tb = cb;
-        t.gap_div = jm::udiv64_make((uint64_t)e->cfg.gap_ms);
-        t.nb = n + n_in;
-        t.bkey = e->d_skey[0];
-        t.bval = e->d_sval[0];
-        t.pk = e->d_spk;
-        t.pkw = e->nacc;
-        t.seg_out = 1;
-        HIPCHK(e, hipEventRecord(e->ev[0], e->stream));
-        sess3_min_kernel<<<grid_for(n + n_in, 1024), kBlock, 0, e->stream>>>(t);
-        const int G = (int)std::max<int64_t>(1, std::min<int64_t>(8192, (n + 2047) / 2048));   // >= 32 waves per CU (latency-bound probes)
-        const int64_t chunk = ((n + G - 1) / G + 255) / 256 * 256;
-        sess3_route_kernel<2><<<G, kBlock, 0, e->stream>>>(t, e->d_ec, chunk);
-        if (n_in > 0) sess3_route_sessions_kernel<<<grid_for(n_in, 256 * 16), kBlock, 0, e->stream>>>(t);
-        HIPCHK(e, hipGetLastError());
-        size_t bytes = 0;
-        const uint32_t* k0 = (const uint32_t*)e->d_skey[0];
-        uint32_t* k1 = (uint32_t*)e->d_skey[1];
-        HIPCHK(e, hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, k0, k1, (const uint32_t*)e->d_sval[0], e->d_sval[1],
-                                                     (int)t.nb, 0, 32, e->stream));
-        if ((rc = ensure_sort_tmp(e, bytes))) return rc;
-        bytes = e->sort_tmp_bytes;
-        HIPCHK(e, hipcub::DeviceRadixSort::SortPairs(e->d_sort_tmp, bytes, k0, k1, (const uint32_t*)e->d_sval[0], e->d_sval[1],
-                                                     (int)t.nb, 0, 32, e->stream));
-        t.bkey = e->d_skey[1];
-        t.bval = e->d_sval[1];
-        if ((rc = launch_segments(e, t, t.nb, true))) return rc;
-        HIPCHK(e, hipEventRecord(e->ev[1], e->stream));
-        if ((rc = read_sess_ctr(e))) return rc;
-        if (e->h_st->error) return FWA_OK;                // reported by the caller
-        if (e->h_sctr->n_special == 0 && e->h_sctr->n_redo == 0) {
-            if ((rc = account_ingest(e))) return rc;
-            e->ingest_launches++;
-            e->ingest_records += n;
-            e->n_ss = (int64_t)e->h_sctr->n_out_sp;
-            e->ss_cur ^= 1;
-            *dropped_out = (int64_t)e->h_st->dropped;
-            e->sess_path = 1;
-            return FWA_OK;
-        }
-        e->cell_skip = 8;                                 // the general path redoes the push (key inserts are idempotent)
-        e->replay_records += n;
-        memset(&z, 0, sizeof(z));
-        z.ts_min = ~0ull;
-        if ((rc = upload(e, e->d_sctr, &z, sizeof(z)))) return rc;
-        HIPCHK(e, hipMemsetAsync(e->d_kflag, 0, (size_t)e->capacity + 1, e->stream));
-        if ((rc = reset_push_status(e))) return rc;
-    }
-    e->sess_path = 0;
-    if (s4_general) {
-        e->cell_skip = 8;                                 // as the cell path: not tried again for 8 pushes
-        e->replay_records += n;
-    } else if (!tried3 && e->cell_skip > 0) {
-        --e->cell_skip;
-    }
-    HIPCHK(e, hipEventRecord(e->ev[0], e->stream));
-    if (n > 0) sess2_classify_kernel<<<grid_for(n, 256 * 32), kBlock, 0, e->stream>>>(s, e->d_ec);
-    if (n_in > 0) sess2_range_kernel<<<grid_for(n_in, 256 * 32), kBlock, 0, e->stream>>>(s);
-    HIPCHK(e, hipGetLastError());
-    if ((rc = read_sess_ctr(e))) return rc;
-    if (e->h_st->error) return FWA_OK;                    // reported by the caller
-    const SessCtr c1 = *e->h_sctr;
-    if (n + n_in == 0 || c1.ts_min > c1.ts_max) {         // nothing to do (empty push, no sessions)
-        *dropped_out = 0;
-        return FWA_OK;
-    }
-    const int64_t lo = jm::unord_i64(c1.ts_min), hi = jm::unord_i64(c1.ts_max);
-    const uint64_t span = (uint64_t)hi - (uint64_t)lo;
-    int tb = 0;
-    while (tb < 64 && (span >> tb) != 0) ++tb;
-    s.base = lo;
-    s.tb = tb;
-    s.all_sp = e->kid_bits + tb > 64 ? 1 : 0;                // start range too wide for one sort key
-    if (s.all_sp) s.tb = 0;
-    s.bkey = e->d_skey[0];
-    s.bval = e->d_sval[0];
-    s.pk = e->d_spk;
-    s.pe = e->d_spe;
-    s.pkw = e->nacc;
-    s.skey = e->d_skey[2];
-    s.sval = e->d_sval[2];
-    sess2_route_kernel<<<(unsigned)((n + n_in + (int64_t)kBlock * kRouteItems - 1) / ((int64_t)kBlock * kRouteItems)), kBlock, 0,
-                         e->stream>>>(s, e->d_ec);
-    HIPCHK(e, hipGetLastError());
-    if ((rc = read_sess_ctr(e))) return rc;
-    const int64_t nb = (int64_t)e->h_sctr->n_bulk, nsp = (int64_t)e->h_sctr->n_sp;
-    s.nb = nb;
-    s.nsp = nsp;
-    s.bend = e->d_send2;
-    s.bmax = e->d_smax;
-    s.bcid = e->d_scid;
-    if (nb > 0) {
-        size_t bytes = 0;
-        HIPCHK(e, hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, (const unsigned long long*)e->d_skey[0], e->d_skey[1],
-                                                     (const uint32_t*)e->d_sval[0], e->d_sval[1], (int)nb, 0, e->kid_bits + tb, e->stream));
-        if ((rc = ensure_sort_tmp(e, bytes))) return rc;
-        bytes = e->sort_tmp_bytes;
-        HIPCHK(e, hipcub::DeviceRadixSort::SortPairs(e->d_sort_tmp, bytes, (const unsigned long long*)e->d_skey[0], e->d_skey[1],
-                                                     (const uint32_t*)e->d_sval[0], e->d_sval[1], (int)nb, 0, e->kid_bits + tb, e->stream));
-        s.bkey = e->d_skey[1];
-        s.bval = e->d_sval[1];
-    }
-    s.seg_out = e->nacc <= 5 ? 1 : 0;
-    if (nb > 0 && s.seg_out) {
-        if ((rc = launch_segments(e, s, nb, false))) return rc;
-    } else if (nb > 0) {
-        size_t bytes = 0;
-        sess2_ends_kernel<<<grid_for(nb, 256 * 32), kBlock, 0, e->stream>>>(s);
-        HIPCHK(e, hipGetLastError());
-        KidEq eq{tb};
-        bytes = 0;
-        HIPCHK(e, hipcub::DeviceScan::InclusiveScanByKey(nullptr, bytes, (const unsigned long long*)s.bkey, (const int64_t*)s.bend,
-                                                         s.bmax, MaxI64(), (int)nb, eq, e->stream));
-        if ((rc = ensure_sort_tmp(e, bytes))) return rc;
-        bytes = e->sort_tmp_bytes;
-        HIPCHK(e, hipcub::DeviceScan::InclusiveScanByKey(e->d_sort_tmp, bytes, (const unsigned long long*)s.bkey, (const int64_t*)s.bend,
-                                                         s.bmax, MaxI64(), (int)nb, eq, e->stream));
-        Sess2Args h = s;
-        h.bcid = e->d_sval[0];                               // head flags (the unsorted payload is dead)
-        sess2_heads_kernel<<<grid_for(nb, 256 * 32), kBlock, 0, e->stream>>>(h);
-        HIPCHK(e, hipGetLastError());
-        bytes = 0;
-        HIPCHK(e, hipcub::DeviceScan::InclusiveSum(nullptr, bytes, (const uint32_t*)h.bcid, s.bcid, (int)nb, e->stream));
-        if ((rc = ensure_sort_tmp(e, bytes))) return rc;
-        bytes = e->sort_tmp_bytes;
-        HIPCHK(e, hipcub::DeviceScan::InclusiveSum(e->d_sort_tmp, bytes, (const uint32_t*)h.bcid, s.bcid, (int)nb, e->stream));
-        sess2_init_kernel<<<grid_for(nb, 256 * 32), kBlock, 0, e->stream>>>(s, e->d_ec);
-        sess2_reduce_kernel<<<grid_for(nb, 256 * 32), kBlock, 0, e->stream>>>(s, e->d_ec);
-        HIPCHK(e, hipGetLastError());
-    }
-    if (nsp > 0) {
-        if (nsp > e->sc_cap) {
-            HIPCHK(e, hipStreamSynchronize(e->stream));
-            if (e->d_sc) HIPCHK(e, hipFree(e->d_sc));
-            e->d_sc = nullptr;
-            e->sc_cap = nsp + nsp / 4 + 1024;
-            HIPCHK(e, hipMalloc(&e->d_sc, 8 * (size_t)e->sc_cap * (2 + e->nacc)));
-        }
-        size_t bytes = 0;
-        const int eb = std::min(64, 32 + e->kid_bits);
-        HIPCHK(e, hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, (const unsigned long long*)e->d_skey[2], e->d_skey[3],
-                                                     (const uint32_t*)e->d_sval[2], e->d_sval[3], (int)nsp, 0, eb, e->stream));
-        if ((rc = ensure_sort_tmp(e, bytes))) return rc;
-        bytes = e->sort_tmp_bytes;
-        HIPCHK(e, hipcub::DeviceRadixSort::SortPairs(e->d_sort_tmp, bytes, (const unsigned long long*)e->d_skey[2], e->d_skey[3],
-                                                     (const uint32_t*)e->d_sval[2], e->d_sval[3], (int)nsp, 0, eb, e->stream));
-        s.skey = e->d_skey[3];
-        s.sval = e->d_sval[3];
-        s.sc_start = e->d_sc;
-        s.sc_end = e->d_sc + nsp;
-        s.sc_acc = (unsigned long long*)(e->d_sc + 2 * nsp);
-        if ((rc = ensure_late_rows(e, e->late_rows + nsp))) return rc;
-        if (!e->d_lr_n) HIPCHK(e, hipMalloc(&e->d_lr_n, 8));
-        if ((rc = upload(e, e->d_lr_n, &e->late_rows, 8))) return rc;
-        s.lr_key = e->lr_col[0];
-        s.lr_start = e->lr_col[1];
-        s.lr_end = e->lr_col[2];
-        for (int j = 0; j < e->cfg.num_aggs; ++j) s.lr_agg[j] = e->lr_col[3 + j];
-        s.lr_n = e->d_lr_n;
-        s.lr_cap = e->lr_cap;
-        sess2_ordered_kernel<<<grid_for(nsp, 256 * 32), kBlock, 0, e->stream>>>(s, e->d_ec);
-        HIPCHK(e, hipGetLastError());
-    }
-    HIPCHK(e, hipEventRecord(e->ev[1], e->stream));
-    uint32_t ncl = 0;
-    unsigned long long lrn = (unsigned long long)e->late_rows;
-    if (nb > 0 && !s.seg_out) HIPCHK(e, hipMemcpyAsync(&ncl, e->d_scid + nb - 1, 4, hipMemcpyDeviceToHost, e->stream));
-    if (nsp > 0) HIPCHK(e, hipMemcpyAsync(&lrn, e->d_lr_n, 8, hipMemcpyDeviceToHost, e->stream));
-    if ((rc = read_sess_ctr(e))) return rc;
-    if ((rc = account_ingest(e))) return rc;
-    e->ingest_launches++;
-    e->ingest_records += n;
-    if (e->h_st->error) return FWA_OK;
-    e->late_rows = (int64_t)lrn;
-    e->n_ss = (int64_t)ncl + (int64_t)e->h_sctr->n_out_sp;
-    e->ss_cur ^= 1;
-    *dropped_out = (int64_t)e->h_st->dropped;
-    return FWA_OK;
-}
-
-// Watermark advance for sessions: late-firing rows of the pushes since the last call first, then every
-// session with prev < end - 1 <= wm; sessions past cleanup are dropped from the list.
-static int fire_sessions(fwa_engine* e, int64_t wm, int64_t* nrows) {
-    const int64_t n_in = e->n_ss;
-    int rc = ensure_out(e, e->late_rows + n_in);
-    if (rc) return rc;
-    if (e->late_rows > 0 && (rc = emit_late_rows(e))) return rc;
-    if ((rc = upload(e, &e->d_st->rows, &e->late_rows, 8))) return rc;
-    e->rows_zero = false;
-    SessCtr z;
-    memset(&z, 0, sizeof(z));
-    if ((rc = upload(e, e->d_sctr, &z, sizeof(z)))) return rc;
-    if ((rc = ensure_sess_lists(e, n_in))) return rc;
-    Sess2FireArgs f;
-    memset(&f, 0, sizeof(f));
-    f.in = e->ss[e->ss_cur];
-    f.out = e->ss[e->ss_cur ^ 1];
-    f.n_in = n_in;
-    f.prev_wm = local_wm(e, e->wm);
-    f.wm = local_wm(e, wm);
-    f.lateness = e->lateness;
-    f.key_table = e->d_keys;
-    f.capacity = e->capacity;
-    f.o_key = e->o_key;
-    f.o_start = e->o_start;
-    f.o_end = e->o_end;
-    for (int j = 0; j < e->cfg.num_aggs; ++j) { f.o_agg[j] = e->o_agg[j]; f.o_null[j] = e->o_null[j]; }
-    f.out_cap = e->out_cap;
-    f.ctr = e->d_sctr;
-    f.st = e->d_st;
-    HIPCHK(e, hipEventRecord(e->ev[2], e->stream));
-    if (n_in > 0)
-        sess2_fire_kernel<<<(unsigned)((n_in + (int64_t)kBlock * kSessFireItems - 1) / ((int64_t)kBlock * kSessFireItems)), kBlock, 0,
-                            e->stream>>>(f, e->d_ec);
-    HIPCHK(e, hipGetLastError());
-    HIPCHK(e, hipEventRecord(e->ev[3], e->stream));
-    if ((rc = read_sess_ctr(e))) return rc;
-    if (e->h_st->error) return fail(e, e->h_st->error, "session fire failed");
-    *nrows = (int64_t)e->h_st->rows;
-    e->n_ss = (int64_t)e->h_sctr->n_keep;
-    e->ss_cur ^= 1;
-    e->late_rows = 0;
-    float ms = 0.f;
-    HIPCHK(e, hipEventElapsedTime(&ms, e->ev[2], e->ev[3]));
-    e->fire_ms += ms;
-    e->fire_launches++;
-    e->fire_rows += *nrows;
-    return FWA_OK;
-}
-
-// Fire kernel over a list of windows (each a union of slots). raw = 1 emits the accumulators and
-// COUNT(*) instead of the final aggregate values (fwa_drain_partials).
-static int emit_late_rows(fwa_engine* e);
-static int upload_windows(fwa_engine* e, const std::vector<FireWindow>& hw, const std::vector<int32_t>& hs);
+#include "ingest_host.inc"            // the two-phase push: plan_v2 .. push_v2
 
 // What a watermark's fire may do beyond emitting (fire_walk_kernel). wm: the watermark being advanced to; a fired
 // window whose slice retire_slices(wm) would release is cleared by the fire itself, provided every row fits the output
@@ -4213,7 +2341,8 @@ static int enqueue_fire_walk(fwa_engine* e, const std::vector<FireWindow>& hw, c
     return FWA_OK;
 }
 
-// Enqueue the fire of windows hw (slot lists hs) into the output columns (rows from row0 on; no host wait).
+// Enqueue the fire of windows hw (each a union of slots, slot lists hs) into the output columns (rows from row0 on; no
+// host wait). raw = 1 emits the accumulators and COUNT(*) instead of the final aggregate values (fwa_drain_partials).
 static int enqueue_fire(fwa_engine* e, const std::vector<FireWindow>& hw, const std::vector<int32_t>& hs, int raw,
                         FireFuse* fu = nullptr) {
     e->rows_zero = false;
@@ -4480,13 +2609,6 @@ static int khash_fill(fwa_engine* e, const int64_t* keys, const int32_t* kh, int
     return FWA_OK;
 }
 
-// Shared ingest driver: two-phase path when allowed, else the v1 kernel; slice-miss replays;
-// lookahead slice allocation; stats.
-static int push_settle(fwa_engine* e, IngestArgs& a, int64_t n, bool ran_v2, bool status_enqueued,
-                       int64_t* late_dropped_out);
-
-static int finish_afire(fwa_engine* e);
-
 // Settle an FWA_PUSH_ASYNC push (the pushes do this first: an asynchronous watermark's fire may keep running).
 static int settle_push(fwa_engine* e) {
     if (!e->pend) return FWA_OK;
@@ -4501,6 +2623,8 @@ static int settle_pending(fwa_engine* e) {
     return settle_push(e);
 }
 
+// Shared ingest driver: two-phase path when allowed, else the v1 kernel; slice-miss replays;
+// lookahead slice allocation; stats.
 static int push_common(fwa_engine* e, IngestArgs& a, int64_t n, bool allow_v2, bool async, int64_t* late_dropped_out) {
     if (e->sparse) return sp_push(e, a, n, async ? nullptr : late_dropped_out);   // settled at once; async: count via stats
     if (++e->push_epoch == INT32_MAX) { e->push_epoch = 1; e->rs_valid = false; }   // (epochs wrap: carried sums dropped)
@@ -4628,10 +2752,6 @@ int fwa_push(fwa_engine* e, const int64_t* keys, const int64_t* ts, const void* 
              const int32_t* key_hash, int64_t n, int32_t flags, int64_t* late_dropped_out) {
     return fwa_push_nullable(e, keys, ts, val_cols, nullptr, key_hash, n, flags, late_dropped_out);
 }
-
-static int push_body(fwa_engine* e, const int64_t* keys, const int64_t* ts, const void* const* val_cols,
-                     const uint8_t* const* null_cols, const int32_t* key_hash, int64_t n, int32_t flags,
-                     int64_t* late_dropped_out);
 
 int fwa_push_nullable(fwa_engine* e, const int64_t* keys, const int64_t* ts, const void* const* val_cols,
                       const uint8_t* const* null_cols, const int32_t* key_hash, int64_t n, int32_t flags,
@@ -4862,8 +2982,6 @@ int fwa_push_partials(fwa_engine* e, const int64_t* keys, const int64_t* slice_t
     return push_common(e, a, n, true, (flags & FWA_PUSH_ASYNC) != 0, late_dropped_out);
 }
 
-static int retire_slices(fwa_engine* e, int64_t wm);
-static int fill_out(fwa_engine* e, int64_t nrows, fwa_out* out);
 // fwa_drain_route's launch: the drained slices straight into per-destination send regions; a region past its
 // capacity is counted, the host grows the regions and launches again (the drain is idempotent until the reset).
 static int launch_drain_route(fwa_engine* e, const std::vector<FireWindow>& hw, const std::vector<int32_t>& hs, int32_t par,
@@ -5305,156 +3423,7 @@ static void snap_header(const fwa_engine* e, int64_t* h, int64_t n) {
     h[27] = e->dist ? e->dist->mask : 0;   // the caller's distinct aggregates (COUNT_DISTINCT, FWA_AGG_DISTINCT); h[28]: their set's entries
 }
 
-// Sessions: the blob's entries are the in-flight sessions (key, start, count, acc_j..., end) bucketed by
-// key group -- the per-key MergingWindowSet mapping plus the window state of WindowOperator
-// (WindowOperator.java:224-238 mergingSetsState / windowState), with the session end as a last column.
-static int snapshot_sessions(fwa_engine* e, fwa_blob* out) {
-    const int64_t n = e->n_ss;
-    const int na = e->cfg.num_aggs, maxp = e->cfg.max_parallelism, nh = e->ec.naggs - e->ec.nout;
-    const bool ph = e->cfg.key_kind == FWA_KEY_PREHASHED;   // + one column: each entry's key.hashCode()
-    const int ncols = 4 + na + nh + (ph ? 1 : 0);
-    const SessList& L = e->ss[e->ss_cur];
-    std::vector<int32_t> khash(ph ? (size_t)e->capacity + 1 : 0);
-    if (ph && n > 0) HIPCHK(e, hipMemcpy(khash.data(), e->d_khash, 4 * ((size_t)e->capacity + 1), hipMemcpyDeviceToHost));
-    std::vector<uint32_t> kid((size_t)n);
-    std::vector<int64_t> st((size_t)n), en((size_t)n), acc((size_t)n * e->nacc);
-    std::vector<unsigned long long> table((size_t)e->capacity + 1);
-    if (n > 0) {
-        HIPCHK(e, hipMemcpy(kid.data(), L.kid, 4 * (size_t)n, hipMemcpyDeviceToHost));
-        HIPCHK(e, hipMemcpy(st.data(), L.start, 8 * (size_t)n, hipMemcpyDeviceToHost));
-        HIPCHK(e, hipMemcpy(en.data(), L.end, 8 * (size_t)n, hipMemcpyDeviceToHost));
-        for (int cc = 0; cc < e->nacc; ++cc)
-            HIPCHK(e, hipMemcpy(acc.data() + (size_t)cc * n, L.acc + (size_t)cc * L.stride, 8 * (size_t)n, hipMemcpyDeviceToHost));
-        HIPCHK(e, hipMemcpy(table.data(), e->d_keys, 8 * (size_t)e->capacity, hipMemcpyDeviceToHost));
-    }
-    std::vector<int32_t> kg((size_t)n);
-    std::vector<int64_t> off((size_t)maxp + 1, 0), key((size_t)n);
-    for (int64_t i = 0; i < n; ++i) {
-        key[i] = (int64_t)kid[i] < e->capacity ? (int64_t)table[kid[i]] : LONG_MIN_J;
-        kg[i] = jm::key_group_of(key[i], e->cfg.key_kind, ph ? khash[kid[i]] : 0, maxp);
-        if (kg[i] < 0) return fail(e, FWA_E_STATE, "state holds a key outside every key group");
-        off[kg[i] + 1]++;
-    }
-    for (int g = 0; g < maxp; ++g) off[g + 1] += off[g];
-    std::vector<int64_t> dsec;                         // COUNT(DISTINCT): the set's live entries behind the body
-    int64_t dm = 0;
-    if (e->dist) { if (int rc = dist_snapshot_section(e, &dsec, &dm)) return rc; }
-    const size_t words0 = kSnapHdr + (size_t)maxp + 1 + (size_t)n * ncols, words = words0 + dsec.size();
-    int64_t* b = (int64_t*)malloc(words * 8);
-    if (!b) return fail(e, FWA_E_OOM, "snapshot blob allocation failed");
-    snap_header(e, b, n);
-    b[28] = dm;
-    if (!dsec.empty()) memcpy(b + words0, dsec.data(), 8 * dsec.size());
-    memcpy(b + kSnapHdr, off.data(), 8 * ((size_t)maxp + 1));
-    int64_t* body = b + kSnapHdr + maxp + 1;
-    std::vector<int64_t> cur(off.begin(), off.end() - 1);
-    for (int64_t i = 0; i < n; ++i) {
-        const int64_t d = cur[kg[i]]++;
-        body[d] = key[i];
-        body[(size_t)n + d] = st[i];
-        body[(size_t)2 * n + d] = acc[i];                                  // COUNT(*)
-        for (int j = 0; j < na; ++j) {
-            const AggDesc& ad = e->ec.agg[j];
-            body[(size_t)(3 + j) * n + d] = ad.acc > 0 ? acc[(size_t)ad.acc * n + i] : acc[i];
-        }
-        for (int h = 0; h < nh; ++h) body[(size_t)(3 + na + h) * n + d] = acc[(size_t)e->ec.agg[e->ec.nout + h].acc * n + i];
-        body[(size_t)(3 + na + nh) * n + d] = en[i];
-        if (ph) body[(size_t)(4 + na + nh) * n + d] = khash[kid[i]];
-    }
-    out->data = b;
-    out->size = (int64_t)(words * 8);
-    return FWA_OK;
-}
-
-__global__ void __launch_bounds__(kBlock) sess2_restore_kernel(Sess2Args a, const int64_t* keys, const int64_t* start,
-                                                               const int64_t* end, const int64_t* const* accs, int64_t m,
-                                                               int64_t at, const EngineConst* __restrict__ cp) {
-    const EngineConst& c = *cp;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t kid = key_slot(a.key_table, a.key_mask, a.seg_log, a.part_bits, keys[i], a.st);
-        if (kid < 0) { a.st->key_full = 1; raise_error(a.st, FWA_E_OOM); continue; }
-        const int64_t o = at + i;
-        a.out.kid[o] = (uint32_t)kid;
-        a.out.start[o] = start[i];
-        a.out.end[o] = end[i];
-        for (int cc = 0; cc < c.nacc; ++cc) a.out.acc[(int64_t)cc * a.out.stride + o] = (unsigned long long)accs[cc][i];
-    }
-}
-
-// Restore sessions: the owned key groups' entries of every blob are appended to the in-flight list
-// (a key lives in one subtask's snapshot, so the lists never overlap); watermark = MIN over the blobs.
-static int restore_sessions(fwa_engine* e, const void* const* blobs, int32_t n_blobs) {
-    const int na = e->cfg.num_aggs, maxp = e->cfg.max_parallelism, nh = e->ec.naggs - e->ec.nout;
-    int64_t wm = LONG_MAX_J;
-    for (int32_t b = 0; b < n_blobs; ++b) {
-        const int64_t* h = (const int64_t*)blobs[b];
-        const int64_t n = h[21];
-        wm = std::min<int64_t>(wm, h[20]);
-        const int64_t* off = h + kSnapHdr;
-        const int64_t lo = off[e->cfg.kg_start], hi = off[e->cfg.kg_end + 1];
-        if (lo < 0 || hi < lo || hi > n) return fail(e, FWA_E_ARG, "corrupt key-group offsets");
-        if (e->dist) {   // the set's entries of this handle's key groups, folded back into block and bit
-            const int ncols = 4 + na + nh + (e->cfg.key_kind == FWA_KEY_PREHASHED ? 1 : 0);
-            if (int rcd = dist_restore_section(e, off + maxp + 1 + (size_t)n * ncols, h[28])) return rcd;
-        }
-        const int64_t m = hi - lo;
-        if (m == 0) continue;
-        const int64_t* body = off + maxp + 1;
-        int rc = ensure_sess_lists(e, e->n_ss + m);
-        if (rc) return rc;
-        // device copies: key, start, end, one column per accumulator (COUNT, then each owner aggregate's)
-        const int nc = 3 + e->nacc;
-        int64_t* d = nullptr;
-        HIPCHK(e, hipMalloc(&d, 8 * (size_t)m * nc));
-        std::vector<const int64_t*> src(nc);
-        src[0] = body + lo;
-        src[1] = body + (size_t)n + lo;
-        src[2] = body + (size_t)(3 + na + nh) * n + lo;
-        src[3] = body + (size_t)2 * n + lo;
-        for (int cc = 1; cc < e->nacc; ++cc) {
-            for (int j = 0; j < na; ++j)
-                if (e->ec.agg[j].acc == cc && !e->ec.agg[j].alias) src[3 + cc] = body + (size_t)(3 + j) * n + lo;
-            for (int h = 0; h < nh; ++h)   // hidden non-NULL counters
-                if (e->ec.agg[e->ec.nout + h].acc == cc) src[3 + cc] = body + (size_t)(3 + na + h) * n + lo;
-        }
-        std::vector<const int64_t*> hacc(e->nacc);
-        for (int c = 0; c < nc; ++c) HIPCHK(e, hipMemcpy(d + (size_t)c * m, src[c], 8 * (size_t)m, hipMemcpyHostToDevice));
-        for (int cc = 0; cc < e->nacc; ++cc) hacc[cc] = d + (size_t)(3 + cc) * m;
-        const int64_t** dacc = nullptr;
-        HIPCHK(e, hipMalloc(&dacc, sizeof(int64_t*) * e->nacc));
-        HIPCHK(e, hipMemcpy(dacc, hacc.data(), sizeof(int64_t*) * e->nacc, hipMemcpyHostToDevice));
-        Sess2Args s;
-        memset(&s, 0, sizeof(s));
-        s.key_table = e->d_keys;
-        s.key_mask = (uint64_t)e->capacity - 1;
-        s.seg_log = e->seg_log;
-        s.part_bits = e->part_bits;
-        s.out = e->ss[e->ss_cur];
-        s.st = e->d_st;
-        sess2_restore_kernel<<<grid_for(m), kBlock, 0, e->stream>>>(s, d, d + m, d + 2 * m, dacc, m, e->n_ss, e->d_ec);
-        HIPCHK(e, hipGetLastError());
-        if (e->d_khash) {                         // PREHASHED: the entries' key.hashCode() (last column) by kid
-            std::vector<int32_t> hv((size_t)m);
-            for (int64_t i = 0; i < m; ++i) hv[i] = (int32_t)body[(size_t)(4 + na + nh) * n + lo + i];
-            int32_t* dh = nullptr;
-            HIPCHK(e, hipMalloc(&dh, sizeof(int32_t) * (size_t)m));
-            HIPCHK(e, hipMemcpyAsync(dh, hv.data(), sizeof(int32_t) * (size_t)m, hipMemcpyHostToDevice, e->stream));
-            khash_fill_kernel<<<grid_for(m), kBlock, 0, e->stream>>>(d, dh, m, e->d_keys, (uint64_t)e->capacity - 1,
-                                                                     e->seg_log, e->part_bits, e->d_khash);
-            HIPCHK(e, hipGetLastError());
-            HIPCHK(e, hipStreamSynchronize(e->stream));
-            (void)hipFree(dh);
-        }
-        rc = sync_status(e);
-        (void)hipFree(d);
-        (void)hipFree(dacc);
-        if (rc) return rc;
-        if (e->h_st->error) return fail(e, e->h_st->error, "key table full: raise fwa_config.key_capacity");
-        e->n_ss += m;
-    }
-    if (n_blobs > 0) e->wm = wm;
-    return FWA_OK;
-}
+#include "sessions_host.inc"          // session push, fire, snapshot and restore (they use snap_header)
 
 // Export every (key, slice) accumulator of every live slice (non-destructive raw fire), then bucket
 // the rows by key group on the host (counting sort) into the blob.

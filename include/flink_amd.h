@@ -256,7 +256,8 @@ enum fwa_status {
     FWA_E_DEVICE = -6,      /* HIP runtime error */
     FWA_E_UNSUPPORTED = -7, /* configuration not supported by this engine build */
     FWA_E_STATE = -8,       /* API misuse (e.g. call on a destroyed handle) */
-    FWA_E_CORRUPT = -9      /* malformed wire bytes (IOException "Corrupt stream", StreamElementSerializer.java:208-210) */
+    FWA_E_CORRUPT = -9,     /* malformed wire bytes (IOException "Corrupt stream", StreamElementSerializer.java:208-210) */
+    FWA_E_INTERNAL = -10    /* an engine invariant does not hold (a bug in the engine, never the caller's input) */
 };
 
 /* Flags for fwa_push */

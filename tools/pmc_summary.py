@@ -22,7 +22,7 @@ EXCLUDE = re.compile(r"fire|sp_refine|sp_agg|generate_kernel|reduce_kernel|eleme
 FIRE = re.compile(r"fire|sp_agg")   # one per step: marks the timed region
 # kernels whose bulk reads are 16 B-per-lane coalesced streaming loads (the calibrated case)
 WIDE = {
-    "partition3_kernel",   # engine.hip load_pairs: ulonglong2 / longlong2 key, ts, value loads
+    "partition3_kernel",   # ingest.inc load_pair: ulonglong2 / longlong2 key, ts, value loads
     "sp_agg_kernel",       # sparse.inc: 16-byte entry loads over contiguous bucket runs
     "wire_scan_kernel",    # wire.hip: 16-byte chunk loads
     "wire_decode_kernel",

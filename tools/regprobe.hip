@@ -2,7 +2,9 @@
 // not harmless on this toolchain: DESIGN.md section 4, "Skewed keys"). Usage:
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 --cuda-device-only -c tools/regprobe.hip -o /tmp/rp.o \
 //         -Rpass-analysis=kernel-resource-usage 2>&1 | grep -E "Function Name|VGPRs|Spill"
-// The instantiation list mirrors the launch sites in flink_amd/csrc/engine.hip (push_v2 and the partition launches).
+// or tools/regprobe.sh. The instantiations are the engine's own: the lists of flink_amd/csrc/ingest_launch.inc, which its
+// launch tables expand too. -DREGPROBE_EXTRA='(const void*)&combine3_kernel<...>,' adds candidates, -DREGPROBE_ONLY_EXTRA
+// leaves the lists out.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -16,71 +18,18 @@
 
 namespace {
 #include "../flink_amd/csrc/ingest.inc"
+#include "../flink_amd/csrc/ingest_launch.inc"
 }  // namespace
+
+#define REGPROBE_P3(NV, IT, VW, KG, PRE, W16, NW, ROLL) (const void*)&partition3_kernel<NV, IT, 1024, VW, KG, PRE, W16, NW, ROLL>,
+#define REGPROBE_C3(IT, NV, LY, PRE, MP, NW, LEAN) (const void*)&combine3_kernel<IT, 2, NV, 1024, LY, PRE, MP, NW, LEAN>,
 
 const void* regprobe_kernels[] = {
 #ifdef REGPROBE_EXTRA
     REGPROBE_EXTRA
 #endif
 #ifndef REGPROBE_ONLY_EXTRA
-    (const void*)&combine3_kernel<2,2,0,1024,0,0,1,0>,
-    (const void*)&combine3_kernel<2,2,0,1024,1,0,1,0>,
-    (const void*)&combine3_kernel<2,2,0,1024,2,0,1,0>,
-    (const void*)&combine3_kernel<2,2,0,1024,2,1,1,0>,
-    (const void*)&combine3_kernel<2,2,1,1024,0,0,1,0>,
-    (const void*)&combine3_kernel<2,2,1,1024,1,0,1,0>,
-    (const void*)&combine3_kernel<2,2,1,1024,1,0,1,1>,
-    (const void*)&combine3_kernel<2,2,1,1024,1,1,1,0>,
-    (const void*)&combine3_kernel<2,2,1,1024,2,0,1,0>,
-    (const void*)&combine3_kernel<2,2,2,1024,0,0,1,0>,
-    (const void*)&combine3_kernel<2,2,2,1024,0,0,1,2>,
-    (const void*)&combine3_kernel<4,2,2,1024,0,0,0,2>,
-    (const void*)&partition3_kernel<2,4,1024,1,0,0,0,2>,
-    (const void*)&combine3_kernel<2,2,2,1024,1,0,1,0>,
-    (const void*)&combine3_kernel<2,2,2,1024,2,0,1,0>,
-    (const void*)&combine3_kernel<4,2,0,1024,0,0,0,0>,
-    (const void*)&combine3_kernel<4,2,0,1024,1,0,0,0>,
-    (const void*)&combine3_kernel<4,2,0,1024,2,0,0,0>,
-    (const void*)&combine3_kernel<4,2,0,1024,2,1,0,0>,
-    (const void*)&combine3_kernel<4,2,1,1024,0,0,0,0>,
-    (const void*)&combine3_kernel<4,2,1,1024,1,0,0,0>,
-    (const void*)&combine3_kernel<4,2,1,1024,1,1,0,0>,
-    (const void*)&combine3_kernel<4,2,1,1024,2,0,0,0>,
-    (const void*)&combine3_kernel<4,2,2,1024,0,0,0,0>,
-    (const void*)&combine3_kernel<4,2,2,1024,1,0,0,0>,
-    (const void*)&combine3_kernel<4,2,2,1024,2,0,0,0>,
-    (const void*)&combine3_kernel<6,2,1,1024,1,0,0,1>,
-    (const void*)&combine3_kernel<6,2,1,1024,1,0,0,1,3>,
-    (const void*)&partition3_kernel<0,4,1024,3,0,1,0,0>,
-    (const void*)&partition3_kernel<0,4,1024,3,1,1,0,0>,
-    (const void*)&partition3_kernel<0,4,1024,3,2,1,0,0>,
-    (const void*)&partition3_kernel<0,8,1024,3,0,0,0,0>,
-    (const void*)&partition3_kernel<0,8,1024,3,1,0,0,0>,
-    (const void*)&partition3_kernel<0,8,1024,3,2,0,0,0>,
-    (const void*)&partition3_kernel<1,4,1024,3,0,1,0,0>,
-    (const void*)&partition3_kernel<1,4,1024,3,1,1,0,0>,
-    (const void*)&partition3_kernel<1,4,1024,3,2,1,0,0>,
-    (const void*)&partition3_kernel<1,6,1024,2,0,0,0,0>,
-    (const void*)&partition3_kernel<1,6,1024,2,0,0,1,0>,
-    (const void*)&partition3_kernel<1,6,1024,2,1,0,0,0>,
-    (const void*)&partition3_kernel<1,6,1024,2,2,0,0,0>,
-    (const void*)&partition3_kernel<1,6,1024,3,0,0,0,0>,
-    (const void*)&partition3_kernel<1,6,1024,3,0,0,1,0>,
-    (const void*)&partition3_kernel<1,6,1024,3,0,0,1,1>,
-    (const void*)&partition3_kernel<1,6,1024,3,0,0,1,1,1>,
-    (const void*)&partition3_kernel<1,6,1024,3,1,0,0,0>,
-    (const void*)&partition3_kernel<1,6,1024,3,2,0,0,0>,
-    (const void*)&partition3_kernel<2,4,1024,0,0,0,0,0>,
-    (const void*)&partition3_kernel<2,4,1024,0,1,0,0,0>,
-    (const void*)&partition3_kernel<2,4,1024,0,2,0,0,0>,
-    (const void*)&partition3_kernel<2,4,1024,1,0,0,0,0>,
-    (const void*)&partition3_kernel<2,4,1024,1,1,0,0,0>,
-    (const void*)&partition3_kernel<2,4,1024,1,2,0,0,0>,
-    (const void*)&partition3_kernel<2,4,1024,2,0,0,0,0>,
-    (const void*)&partition3_kernel<2,4,1024,2,1,0,0,0>,
-    (const void*)&partition3_kernel<2,4,1024,2,2,0,0,0>,
-    (const void*)&partition3_kernel<2,4,1024,3,0,0,0,0>,
-    (const void*)&partition3_kernel<2,4,1024,3,1,0,0,0>,
-    (const void*)&partition3_kernel<2,4,1024,3,2,0,0,0>,
+    FWA_P3_INSTANCES(REGPROBE_P3)
+    FWA_C3_INSTANCES(REGPROBE_C3)
 #endif
 };
