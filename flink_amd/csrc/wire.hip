@@ -30,6 +30,14 @@
 // in which the record's lane checks each DECIMAL column's slot against the row, assembles the big-endian bytes in LDS
 // and stores the sign-extended 128-bit value with one 16-byte store. Schemas without one run the kernels they ran.
 //
+// TUPLE values with java.lang.String fields (FWA_FIELD_JSTRING: StringSerializer -> StringValue.writeString, len + 1 as
+// a varint, then every UTF-16 code unit as a varint of 1..3 bytes; null is 00) vary in length as well and are a third
+// instantiation (JS) of scan and decode: a record header is valid on its length alone (a weak filter, and a sound one:
+// see element_at), and the decode pass walks the fields with a running cursor, checks each String's canonical form and
+// writes the same per-record length / NULL flag / byte offset arrays as the STRING path, so fwa_wire_strings_of serves
+// both. A value is handed on as its char bytes as they stand on the wire. fwa_jstring_hash is String.hashCode() over
+// those bytes. The two instantiations above are the code as it was.
+//
 // HBM traffic: the wire bytes are read twice (scan, decode), the maps are S x 4 B per 4 KiB chunk, the
 // columns are written once. Bound: HBM (wire decoder).
 //
@@ -125,7 +133,14 @@ __device__ __forceinline__ void stage_chunk(uint32_t* words, const uint8_t* __re
 // equality, which keeps false candidates as rare as the exact length does for fixed rows), the element is within the
 // 249-byte ceiling (else 3: TOO LONG) and the RowKind byte is INSERT (else 4, *tag = 256 + RowKind). The order of
 // these checks is part of the format the tests' reference decoder restates.
-template <bool VAR>
+//
+// JS (TUPLE values with JSTRING fields; with VAR): a tuple has no size int to cross-check, so a record header is
+// accepted on its length alone: at least body[0] / body[1] (tag, [timestamp], the fixed fields, one byte per JSTRING
+// field), at most the ceiling (else 3), the element inside the stream (else 1). The filter is weak -- any four bytes
+// that read as 2..249 in front of a 00 / 01 pass it -- and that is sound: a false candidate only costs the scan a walk
+// whose map entry nobody composes with, because every entry is the exact exit of the chain from that offset and the
+// composition follows the one chain that starts at byte 0 of the call.
+template <bool VAR, bool JS = false>
 __device__ __forceinline__ int element_at(const Lds& b, int p, int rem, const WireConst& w, uint32_t* len,
                                           int* tag) {
     if (p + 5 > rem) return 1;
@@ -134,7 +149,15 @@ __device__ __forceinline__ int element_at(const Lds& b, int p, int rem, const Wi
     *tag = t;
     const int32_t want = t == 0 ? w.body[0] : t == 1 ? w.body[1] : t == 2 ? w.body[2] : t == 3 ? w.body[3]
                        : t == 4 ? w.body[4] : t == 5 ? w.body[5] : -1;
-    if constexpr (VAR) {
+    if constexpr (JS) {
+        if (t <= 1) {
+            if (l < (uint32_t)want) return 2;
+            if (l > kMaxBody) return 3;
+            if (p + 4 + (int)l > rem) return 1;
+            *len = l;
+            return 0;
+        }
+    } else if constexpr (VAR) {
         if (t <= 1) {
             const int hdr = t == 0 ? 13 : 5;                       // tag, [timestamp], size int
             if (l < (uint32_t)want) return 2;
@@ -165,7 +188,7 @@ __device__ __forceinline__ int element_at(const Lds& b, int p, int rem, const Wi
 // VAR: rows whose strings are all inline have one size and the speculation runs as above. When it misses twice in
 // a row (k = 0: sizes alternate), the wave lists up to 64 elements by uniform scalar steps, lane i keeping the i-th,
 // and the lanes visit them in parallel; it goes back to speculating after a list whose elements all had one size.
-template <bool VAR, class F>
+template <bool VAR, bool JS = false, class F>
 __device__ __forceinline__ int wave_walk(const Lds& b, int p, int remi, const WireConst& w, uint32_t* nrec,
                                          uint32_t* nevt, int* stop, int* badtag, F&& visit) {
     const int lane = threadIdx.x & 63;
@@ -179,7 +202,7 @@ __device__ __forceinline__ int wave_walk(const Lds& b, int p, int remi, const Wi
             const int pos = p + lane * R;
             uint32_t len = 0;
             int tag = 0;
-            const bool ok = pos < kChunk && element_at<VAR>(b, pos, remi, w, &len, &tag) == 0 && (int)len + 4 == R;
+            const bool ok = pos < kChunk && element_at<VAR, JS>(b, pos, remi, w, &len, &tag) == 0 && (int)len + 4 == R;
             const uint64_t m = __ballot(ok);
             const int k = ~m == 0 ? 64 : __builtin_ctzll(~m);
             const bool mine = lane < k;
@@ -206,7 +229,7 @@ __device__ __forceinline__ int wave_walk(const Lds& b, int p, int remi, const Wi
                 }
                 uint32_t len = 0;
                 int tag = 0;
-                const bool ok = lane < cnt && element_at<VAR>(b, mypos, remi, w, &len, &tag) == 0;
+                const bool ok = lane < cnt && element_at<VAR, JS>(b, mypos, remi, w, &len, &tag) == 0;
                 const uint64_t m = __ballot(ok);
                 const int k = ~m == 0 ? 64 : __builtin_ctzll(~m);   // <= cnt
                 const bool mine = lane < k;
@@ -225,7 +248,7 @@ __device__ __forceinline__ int wave_walk(const Lds& b, int p, int remi, const Wi
         }
         uint32_t len = 0;                                          // scalar step at p (uniform)
         int tag = 0;
-        const int st = element_at<VAR>(b, p, remi, w, &len, &tag);
+        const int st = element_at<VAR, JS>(b, p, remi, w, &len, &tag);
         if (st) { *nrec = nr; *nevt = ne; *stop = p; *badtag = tag; return st; }
         if (lane == 0) visit(p, tag, nr, ne);
         if (tag <= 1) ++nr; else ++ne;
@@ -288,7 +311,7 @@ __device__ __forceinline__ int stage_pf(uint32_t* buf, const uint8_t* __restrict
 // first one leaves, at every element start below S, the records / events before it (vis[]); the map entries of those
 // later candidates are the walk's exit and its totals minus that rank, and they are not walked again. ----
 constexpr uint32_t kVisMark = 1u << 31, kVisDone = 1u << 30;
-template <bool VAR>
+template <bool VAR, bool JS = false>
 __global__ __launch_bounds__(64) void wire_scan_kernel(const uint8_t* __restrict__ in, int64_t nbytes,
                                                         int64_t nchunks, WireConst w, bool aligned,
                                                         uint32_t* __restrict__ map0) {
@@ -306,7 +329,7 @@ __global__ __launch_bounds__(64) void wire_scan_kernel(const uint8_t* __restrict
             const int e = e0 + lane;
             uint32_t len = 0;
             int tag = 0;
-            int first = e < w.step ? element_at<VAR>(b, e, remi, w, &len, &tag) : kNone;
+            int first = e < w.step ? element_at<VAR, JS>(b, e, remi, w, &len, &tag) : kNone;
             if constexpr (VAR)
                 if (first == 0 && (vis[e] & kVisDone)) first = kNone;  // settled by an earlier candidate's walk
             if (first >= 1 && first < kNone) map0[c * w.step + e] = first == 1 ? kNxtEnd : kNxtCorrupt;
@@ -318,7 +341,7 @@ __global__ __launch_bounds__(64) void wire_scan_kernel(const uint8_t* __restrict
                 int stop = 0, bt = 0;
                 if constexpr (VAR) {
                     const int S = w.step;
-                    const int r = wave_walk<VAR>(b, e0 + j, remi, w, &nrec, &nevt, &stop, &bt,
+                    const int r = wave_walk<VAR, JS>(b, e0 + j, remi, w, &nrec, &nevt, &stop, &bt,
                                                  [&](int pos, int, uint32_t rb, uint32_t eb) {
                                                      if (pos < S) vis[pos] = kVisMark | rb | (eb << 12);
                                                  });
@@ -447,6 +470,7 @@ struct DecodeOut {
 constexpr int kErrTooLong = 512;       // WireStatus.err_tag of an element over the ceiling (>= 256: RowKind + 256)
 constexpr int kErrSlot = 513;          // ... of a STRING slot pointing outside its row
 constexpr int kErrDecSlot = 514;       // ... of a DECIMAL slot: bytes outside the row's variable-length part, 0 or > 16 of them
+constexpr int kErrJstr = 515;          // ... of a TUPLE value whose field walk does not end at the element's end
 
 __device__ void raise_err(WireStatus* st, int code, int tag, int64_t pos) {
     if (atomicCAS(&st->error, 0, code) == 0) {
@@ -480,7 +504,15 @@ __device__ __forceinline__ bool field_null(const Lds& b, int row, int f) {   // 
 // RowKind; every STRING slot is checked against the row here, before anything reads the value's bytes.
 // DEC (with VAR): the schema has DECIMAL value columns; their slots are checked the same way, then the 1..16 big-endian
 // bytes (inside the row, so inside the staged chunk and its halo) are read from LDS by the record's lane ----
-template <bool VAR, bool DEC = false>
+//
+// JS (with VAR): TUPLE values with JSTRING fields (StringSerializer -> StringValue.writeString, flink-core/.../types/
+// StringValue.java:  len + 1 as a varint of 7-bit groups, low group first, then every UTF-16 code unit coded the same
+// way, 1..3 bytes). Nothing has a fixed offset, so the record's lane walks the fields in order from the element's bytes
+// in LDS with a running cursor: fixed fields big-endian at the cursor, a JSTRING as its length varint and then `len`
+// chars, each checked for the canonical form (at most three groups, a last group that is not zero behind a
+// continuation, a third group <= 3). A char ends at its first byte below 0x80, so skipping n chars is counting n such
+// bytes. No byte at or past the element's end is read, and the cursor must stand exactly there after the last field.
+template <bool VAR, bool DEC = false, bool JS = false>
 __global__ __launch_bounds__(64) void wire_decode_kernel(const uint8_t* __restrict__ in, int64_t nbytes, int64_t nchunks,
                                                           WireConst w, bool aligned, const uint8_t* __restrict__ c_ent,
                                                           const uint64_t* __restrict__ c_rec,
@@ -502,6 +534,70 @@ __global__ __launch_bounds__(64) void wire_decode_kernel(const uint8_t* __restri
                 int64_t ts = (int64_t)0x8000000000000000LL;          // StreamRecord without timestamp
                 if (tag == FWA_TAG_REC_WITH_TIMESTAMP) { ts = (int64_t)b.be64(q); q += 8; }
                 bool knull = false;
+                if constexpr (JS) {
+                    const int end = p + 4 + (int)b.be32(p);          // <= p + 253, inside the staged bytes (element_at)
+                    bool bad = false;
+                    int k = 0;
+                    for (int f = 0; f < w.arity && !bad; ++f) {
+                        const int t = w.ftype[f];
+                        if (t != FWA_FIELD_JSTRING) {
+                            const int nb = (t == FWA_FIELD_LONG || t == FWA_FIELD_DOUBLE) ? 8 : 4;
+                            if (q + nb > end) { bad = true; break; }
+                            uint64_t v;
+                            if (nb == 8) v = b.be64(q);
+                            else { const uint32_t x = b.be32(q); v = t == FWA_FIELD_INT ? (uint64_t)(int64_t)(int32_t)x : (uint64_t)x; }
+                            q += nb;
+                            if (f == w.ts_field) ts = (int64_t)v;
+                            for (int j = 0; j < w.num_cols; ++j) {
+                                if (w.col_field[j] != f) continue;
+                                if (t == FWA_FIELD_FLOAT) reinterpret_cast<uint32_t*>(o.col[j])[g] = (uint32_t)v;
+                                else reinterpret_cast<uint64_t*>(o.col[j])[g] = v;
+                            }
+                            continue;
+                        }
+                        // StringValue.readString: the length varint (an int: at most 5 groups), 0 = null, else len + 1
+                        uint64_t lv = 0;
+                        int sh = 0, first = -1;
+                        for (;;) {
+                            if (q >= end || sh > 28) { bad = true; break; }
+                            const uint32_t c = b.byte(q++);
+                            if (first < 0) first = (int)c;
+                            lv |= (uint64_t)(c & 0x7f) << sh;
+                            sh += 7;
+                            if (c < 0x80) break;
+                        }
+                        if (bad) break;
+                        const bool isnull = first == 0;
+                        if (!isnull && lv == 0) { bad = true; break; }    // 80 00: a length of -1 to the reference reader
+                        const int64_t nch = isnull ? 0 : (int64_t)lv - 1;
+                        if (nch > end - q) { bad = true; break; }         // every char has at least one byte
+                        const int v0 = q;
+                        int run = 0;                                      // continuation bytes of the char under the cursor
+                        for (int64_t left = nch; left > 0;) {
+                            if (run == 0 && left >= 4 && q + 4 <= end) {      // four one-byte chars (ASCII text) at once
+                                if (!(b.u32le(q) & 0x80808080u)) { q += 4; left -= 4; continue; }
+                            }
+                            if (q >= end) { bad = true; break; }
+                            const uint32_t c = b.byte(q++);
+                            if (c >= 0x80) {
+                                if (++run >= 3) { bad = true; break; }    // a fourth group
+                                continue;
+                            }
+                            if ((run > 0 && c == 0) || (run == 2 && c > 3)) { bad = true; break; }
+                            run = 0;
+                            --left;
+                        }
+                        if (bad) break;
+                        const int64_t at = k * o.str_stride + g;
+                        o.str_len[at] = q - v0;
+                        o.str_src[at] = cs + v0;
+                        o.str_null[at] = isnull;
+                        ++k;
+                    }
+                    if (bad || q != end) { raise_err(o.st, FWA_E_CORRUPT, kErrJstr, cs + p); return; }
+                    o.ts[g] = ts;
+                    return;
+                }
                 if constexpr (VAR) {
                     const int size = (int)b.be32(q);                 // == L - header, <= 249 (element_at)
                     q += 4;
@@ -595,7 +691,7 @@ __global__ __launch_bounds__(64) void wire_decode_kernel(const uint8_t* __restri
         };
         uint32_t nrec = 0, nevt = 0;
         int stop = 0, bt = 0;
-        const int r = wave_walk<VAR>(b, (int)ent, remi, w, &nrec, &nevt, &stop, &bt, visit);
+        const int r = wave_walk<VAR, JS>(b, (int)ent, remi, w, &nrec, &nevt, &stop, &bt, visit);
         if (threadIdx.x == 0) {
             if (r == 1) o.st->consumed = cs + stop;
             else if (r == 2) raise_err(o.st, FWA_E_CORRUPT, bt, cs + stop);
@@ -647,6 +743,59 @@ __global__ __launch_bounds__(256) void wire_len_sum_kernel(const int32_t* __rest
         s += (unsigned long long)(uint32_t)len[i];
     for (int d = 32; d > 0; d >>= 1) s += __shfl_down(s, d, 64);
     if ((threadIdx.x & 63) == 0 && s) atomicAdd(total, s);
+}
+
+// ---- String.hashCode() of values in the canonical char-byte form (fwa_jstring_hash). Keys are short, so a lane takes
+// a value and a wave 64 consecutive ones, whose bytes are one contiguous run of the Arrow bytes. The run is brought into
+// LDS a tile at a time, coalesced: 16-byte loads for the aligned middle, byte loads for the ragged head and tail (the
+// tile keeps the run's 16-byte phase), so no lane issues strided byte loads to HBM. Each lane then reads the part of
+// its value that lies in the tile from LDS and carries (hash, char under assembly) to the next tile; a value of any
+// length is hashed that way, and a run of 64 five-byte keys is one tile.
+// h = 31 * h + c per code unit; a code unit's 7-bit groups arrive low group first and it ends at a byte below 0x80. ----
+constexpr int kHashTile = 4096;
+__global__ __launch_bounds__(64) void wire_jstring_hash_kernel(const int32_t* __restrict__ off, const uint8_t* __restrict__ bytes,
+                                                                const uint8_t* __restrict__ nulls, int64_t n,
+                                                                int32_t* __restrict__ out) {
+    __shared__ u32x4 tile[kHashTile / 16 + 1];
+    const uint8_t* tb = reinterpret_cast<const uint8_t*>(tile);
+    uint8_t* tw = reinterpret_cast<uint8_t*>(tile);
+    const int lane = threadIdx.x;
+    const int64_t nwaves = (n + 63) / 64;
+    for (int64_t wv = blockIdx.x; wv < nwaves; wv += gridDim.x) {
+        const int64_t base = wv * 64;
+        const int m = (int)std::min<int64_t>(64, n - base);
+        const int64_t g = base + lane;
+        const int64_t r0 = off[base], r1 = off[base + m];          // the wave's run of bytes
+        const bool live = lane < m && !(nulls && nulls[g]);
+        const int64_t s = lane < m ? off[g] : r1, e = lane < m ? off[g + 1] : r1;
+        uint32_t h = 0, ch = 0;
+        int sh = 0;
+        for (int64_t t0 = r0; t0 < r1;) {
+            const uint8_t* __restrict__ src = bytes + t0;
+            const int skew = (int)(reinterpret_cast<uintptr_t>(src) & 15);
+            const int len = (int)std::min<int64_t>(r1 - t0, kHashTile - skew);
+            __syncthreads();                                          // the previous tile has been read
+            const int head = std::min(len, (16 - skew) & 15);
+            for (int j = lane; j < head; j += 64) tw[skew + j] = src[j];
+            const int nfull = (len - head) >> 4, v0 = (skew + head) >> 4;
+            const u32x4* __restrict__ sv = reinterpret_cast<const u32x4*>(src + head);
+            for (int i = lane; i < nfull; i += 64) tile[v0 + i] = sv[i];
+            for (int j = head + (nfull << 4) + lane; j < len; j += 64) tw[skew + j] = src[j];
+            __syncthreads();
+            if (live) {
+                const int a = (int)(std::max<int64_t>(s, t0) - t0), z = (int)(std::min<int64_t>(e, t0 + len) - t0);
+                for (int j = a; j < z; ++j) {
+                    const uint32_t c = tb[skew + j];
+                    ch |= (c & 0x7f) << sh;
+                    sh += 7;
+                    if (c < 0x80) { h = 31u * h + (ch & 0xffffu); ch = 0; sh = 0; }
+                    else if (sh > 14) sh = 14;                        // (not canonical: keep the shift defined)
+                }
+            }
+            t0 += len;
+        }
+        if (lane < m) out[g] = live ? (int32_t)h : 0;
+    }
 }
 
 }  // namespace
@@ -808,11 +957,19 @@ int fwa_wire_create(const fwa_wire_schema* s, fwa_wire_decoder** out) {
     if (s->num_cols < 0 || s->num_cols > FWA_MAX_COLS) return bad(FWA_E_ARG, "num_cols out of range");
     w.format = s->format;
     w.arity = s->arity;
-    int off = 0;
+    int off = 0, njs = 0;
     w.nullbits = ((s->arity + 63 + 8) / 64) * 8;                  // BinaryRowData.calculateBitSetWidthInBytes
     for (int f = 0; f < s->arity; ++f) {
         const int t = s->field[f];
-        if (t < FWA_FIELD_LONG || (t > FWA_FIELD_STRING && t != FWA_FIELD_DECIMAL)) return bad(FWA_E_UNSUPPORTED, "unsupported field type");
+        if (t < FWA_FIELD_LONG || (t > FWA_FIELD_STRING && t != FWA_FIELD_DECIMAL && t != FWA_FIELD_JSTRING))
+            return bad(FWA_E_UNSUPPORTED, "unsupported field type");
+        if (t == FWA_FIELD_JSTRING) {
+            if (s->format != FWA_WIRE_TUPLE)
+                return bad(FWA_E_UNSUPPORTED, "JSTRING fields (StringSerializer) are decoded in TUPLE values only: a row's "
+                                              "CHAR / VARCHAR / STRING field is FWA_FIELD_STRING");
+            w.str_field[w.nstr++] = f;
+            ++njs;
+        }
         if (t == FWA_FIELD_DECIMAL) {
             if (s->format != FWA_WIRE_ROWDATA)
                 return bad(FWA_E_UNSUPPORTED, "DECIMAL fields are decoded in ROWDATA rows only: a Tuple's BigDecSerializer is "
@@ -826,9 +983,12 @@ int fwa_wire_create(const fwa_wire_schema* s, fwa_wire_decoder** out) {
             w.str_field[w.nstr++] = f;
         }
         w.ftype[f] = t;
-        if (s->format == FWA_WIRE_TUPLE) { w.foff[f] = off; off += field_bytes(t); }
-        else w.foff[f] = w.nullbits + 8 * f;
+        if (s->format == FWA_WIRE_TUPLE) { w.foff[f] = off; off += t == FWA_FIELD_JSTRING ? 1 : field_bytes(t); }
+        else w.foff[f] = w.nullbits + 8 * f;                      // (JSTRING schemas: the shortest value; foff is not used)
     }
+    if (njs > 0 && s->key_field != -1)
+        return bad(FWA_E_ARG, "a schema with JSTRING fields has key_field -1: the key is built from the string (fwa_keydict_encode, "
+                              "fwa_jstring_hash)");
     auto integral = [&](int f) { return f >= 0 && f < s->arity && (w.ftype[f] == FWA_FIELD_LONG || w.ftype[f] == FWA_FIELD_INT); };
     if (!(s->key_field == -1 && w.nstr > 0) && !integral(s->key_field))
         return bad(FWA_E_ARG, "key_field must be a LONG or INT field (or -1 in a schema with STRING fields)");
@@ -839,6 +999,7 @@ int fwa_wire_create(const fwa_wire_schema* s, fwa_wire_decoder** out) {
     for (int j = 0; j < s->num_cols; ++j) {
         if (s->col_field[j] < 0 || s->col_field[j] >= s->arity) return bad(FWA_E_ARG, "col_field out of range");
         if (w.ftype[s->col_field[j]] == FWA_FIELD_STRING) return bad(FWA_E_ARG, "a STRING field cannot be a value column");
+        if (w.ftype[s->col_field[j]] == FWA_FIELD_JSTRING) return bad(FWA_E_ARG, "a JSTRING field cannot be a value column");
         if (w.ftype[s->col_field[j]] == FWA_FIELD_DECIMAL) ++w.ndec;
         w.col_field[j] = s->col_field[j];
     }
@@ -961,7 +1122,9 @@ int fwa_wire_decode(fwa_wire_decoder* d, const uint8_t* bytes, int64_t nbytes, i
     WCK(hipEventRecord(d->ev[0], st));
     const unsigned grid = (unsigned)std::min<int64_t>(nchunks, kPersistBlocks);
     const bool var = w.nstr + w.ndecf > 0;
-    if (var) hipLaunchKernelGGL(wire_scan_kernel<true>, dim3(grid), dim3(64), 0, st, in, nbytes, nchunks, w, aligned, d->map0);
+    const bool js = var && w.format == FWA_WIRE_TUPLE;           // JSTRING fields: the only variable-length TUPLE values
+    if (js) hipLaunchKernelGGL((wire_scan_kernel<true, true>), dim3(grid), dim3(64), 0, st, in, nbytes, nchunks, w, aligned, d->map0);
+    else if (var) hipLaunchKernelGGL(wire_scan_kernel<true>, dim3(grid), dim3(64), 0, st, in, nbytes, nchunks, w, aligned, d->map0);
     else hipLaunchKernelGGL(wire_scan_kernel<false>, dim3(grid), dim3(64), 0, st, in, nbytes, nchunks, w, aligned, d->map0);
     WCK(hipGetLastError());
     WCK(hipEventRecord(d->ev[1], st));
@@ -1012,7 +1175,9 @@ int fwa_wire_decode(fwa_wire_decoder* d, const uint8_t* bytes, int64_t nbytes, i
         o.evt_tag = d->d_evt_tag;
         o.evt_val = d->d_evt_val;
         o.evt_cap = d->evt_cap;
-        if (w.ndec > 0) hipLaunchKernelGGL((wire_decode_kernel<true, true>), dim3(grid), dim3(64), 0, st, in, nbytes, nchunks, w,
+        if (js) hipLaunchKernelGGL((wire_decode_kernel<true, false, true>), dim3(grid), dim3(64), 0, st, in, nbytes, nchunks, w,
+                                   aligned, d->ent, d->rec, d->evt, o);
+        else if (w.ndec > 0) hipLaunchKernelGGL((wire_decode_kernel<true, true>), dim3(grid), dim3(64), 0, st, in, nbytes, nchunks, w,
                                            aligned, d->ent, d->rec, d->evt, o);
         else if (var) hipLaunchKernelGGL(wire_decode_kernel<true>, dim3(grid), dim3(64), 0, st, in, nbytes, nchunks, w, aligned,
                                          d->ent, d->rec, d->evt, o);
@@ -1039,11 +1204,12 @@ int fwa_wire_decode(fwa_wire_decoder* d, const uint8_t* bytes, int64_t nbytes, i
         d->stats.decode_ms += ms_all;
         const WireStatus& hs = *d->h_st;
         if (hs.error) {
-            char m[160];
+            char m[256];
             if (hs.error == FWA_E_CORRUPT && hs.err_tag < 256) snprintf(m, sizeof m, "Corrupt stream, found tag: %d (element at byte %lld)", hs.err_tag, (long long)hs.err_pos);
             else if (hs.error == FWA_E_ARG) snprintf(m, sizeof m, "NULL rowtime field in the row at byte %lld", (long long)hs.err_pos);
             else if (hs.err_tag == kErrSlot) snprintf(m, sizeof m, "Corrupt stream: a STRING slot points outside its row (record at byte %lld)", (long long)hs.err_pos);
             else if (hs.err_tag == kErrDecSlot) snprintf(m, sizeof m, "Corrupt stream: a DECIMAL slot names bytes outside its row, none or more than 16 (record at byte %lld)", (long long)hs.err_pos);
+            else if (hs.err_tag == kErrJstr) snprintf(m, sizeof m, "Corrupt stream: the fields of a TUPLE value do not end at its element's end, or a String is not in StringValue's canonical form (record at byte %lld)", (long long)hs.err_pos);
             else if (hs.err_tag == kErrTooLong) snprintf(m, sizeof m, "element longer than the %d-byte limit at byte %lld", (int)kMaxBody, (long long)hs.err_pos);
             else if (hs.err_tag >= 256) snprintf(m, sizeof m, "RowKind %d at byte %lld: window aggregation consumes insert-only rows", hs.err_tag - 256, (long long)hs.err_pos);
             else snprintf(m, sizeof m, "row size differs from the schema's fixed-length row at byte %lld", (long long)hs.err_pos);
@@ -1086,7 +1252,7 @@ int fwa_wire_strings_of(fwa_wire_decoder* d, int32_t field, fwa_wire_strings* ou
     const WireConst& w = d->w;
     int k = -1;
     for (int i = 0; i < w.nstr; ++i) if (w.str_field[i] == field) k = i;
-    if (k < 0) return fail(d, FWA_E_ARG, "not a STRING field of the schema");
+    if (k < 0) return fail(d, FWA_E_ARG, "not a STRING / JSTRING field of the schema");
     if (!d->str_valid) return fail(d, FWA_E_STATE, "no decoded batch: strings follow a successful fwa_wire_decode");
     const int64_t n = d->last_nrec, stride = d->out_cap + 1;
     const int32_t* len = d->str_len + k * stride;
@@ -1132,6 +1298,17 @@ int fwa_wire_strings_of(fwa_wire_decoder* d, int32_t field, fwa_wire_strings* ou
     out->bytes = d->str_bytes[k];
     out->null = d->str_null + k * stride;
     out->total_bytes = d->str_total[k];
+    return FWA_OK;
+}
+
+int fwa_jstring_hash(const int32_t* offsets, const uint8_t* bytes, const uint8_t* nulls, int64_t n, int32_t* out,
+                     int32_t device) {
+    if (n < 0 || n >= (1ll << 31) || (n > 0 && (!offsets || !out))) return FWA_E_ARG;
+    if (n == 0) return FWA_OK;
+    if (hipSetDevice(device) != hipSuccess) return FWA_E_DEVICE;
+    const unsigned grid = (unsigned)std::min<int64_t>((n + 63) / 64, 256 * 32);
+    hipLaunchKernelGGL(wire_jstring_hash_kernel, dim3(grid), dim3(64), 0, 0, offsets, bytes, nulls, n, out);
+    if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return FWA_E_DEVICE;
     return FWA_OK;
 }
 

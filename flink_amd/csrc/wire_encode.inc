@@ -30,6 +30,13 @@
 //     length. A NULL result is setNullAt (RowDataSerializer.toBinaryRow :196-212): the bit, a zero slot, nothing reserved.
 //     Schemas without a DECIMAL field run the instantiations they ran.
 //
+//   TUPLE values with JSTRING fields (JS) are a third instantiation of the three passes. A String field is the varint of
+//     its code-unit count + 1 and then the key dictionary's char bytes verbatim (the canonical form: the count is the
+//     number of bytes below 0x80, counted eight bytes at a time), and the fields behind it follow unaligned, so the row's
+//     lane walks the fields with a running position instead of the schema's offsets. Staged tiles take the bytes
+//     through the sink like a STRING's; in the direct path the wave goes field by field -- the lanes write their fixed
+//     fields and length prefixes, then the field's values are copied byte-parallel as above.
+//
 // The trailing events (a handful) are laid out on the host and copied behind the rows on the encoder's stream.
 // HBM traffic: every column read once, every output byte written once; VAR adds 16 B per row of sizes / offsets.
 
@@ -49,8 +56,10 @@ struct EncConst {
     int32_t scls[FWA_WIRE_MAX_FIELDS];       // EncClass of the source column
     int32_t adj[FWA_WIRE_MAX_FIELDS];        // added to an int64 source (WIN_TIME: -1)
     int32_t foff[FWA_WIRE_MAX_FIELDS];       // offset of the field (TUPLE) / its slot (ROWDATA) in the element
-    int32_t ndec;                            // DECIMAL fields (> 0: elements vary in size too); last, so that the members
-                                             // above keep their places in the kernel argument
+    int32_t ndec;                            // DECIMAL fields (> 0: elements vary in size too); behind the members above,
+                                             // so that those keep their places in the kernel argument
+    int32_t njs;                             // JSTRING fields of a TUPLE value (> 0: elements vary in size; efix counts
+                                             // none of their bytes and foff is not used)
 };
 
 struct EncCols {
@@ -111,16 +120,68 @@ __device__ __forceinline__ uint64_t enc_str_bytes(const uint8_t* __restrict__ p,
     return v;
 }
 
+// Code units of a value in the canonical char-byte form: its bytes below 0x80.
+__device__ __forceinline__ int64_t enc_js_chars(const uint8_t* __restrict__ p, int64_t len, int64_t so, int64_t end) {
+    int64_t cnt = 0;
+    for (int64_t o = 0; o < len; o += 8) {
+        const int nb = (int)std::min<int64_t>(8, len - o);
+        const uint64_t v = enc_str_bytes(p + o, nb, so + o + 8 <= end);
+        cnt += nb - __builtin_popcountll(v & 0x8080808080808080ull);
+    }
+    return cnt;
+}
+
+// StringValue.writeString's length prefix: x in 7-bit groups, low group first, as little-endian bytes; *nb = 1..5.
+__device__ __forceinline__ uint64_t enc_varint(uint64_t x, int* nb) {
+    uint64_t v = 0;
+    int i = 0;
+    for (;; ++i) {
+        const uint64_t grp = x & 0x7f;
+        x >>= 7;
+        v |= (grp | (x ? 0x80ull : 0ull)) << (8 * i);
+        if (!x) break;
+    }
+    *nb = i + 1;
+    return v;
+}
+
+__device__ __forceinline__ int enc_varint_len(uint64_t x) { return x < (1ull << 7) ? 1 : x < (1ull << 14) ? 2 : x < (1ull << 21) ? 3 : x < (1ull << 28) ? 4 : 5; }
+
 // Row g's element (esize: its bytes, prefix included). COPY: with the bytes of its STRING values, 8 at a time through
 // the sink; otherwise those are left to the caller's copy pass. n: the rows of the call (the columns' end).
 // DEC: the schema has DECIMAL fields; their 16 reserved bytes always go through the sink.
-template <bool VAR, bool COPY, bool DEC, class Sink>
+template <bool VAR, bool COPY, bool DEC, bool JS = false, class Sink>
 __device__ __forceinline__ void enc_element(const EncConst& c, const EncCols& k, int64_t g, int64_t esize, const Sink& s,
                                             int64_t n = 0) {
     const uint32_t L = (uint32_t)(esize - 4);
     s.put(0, (uint64_t)__builtin_bswap32(L) | ((uint64_t)(c.with_ts ? FWA_TAG_REC_WITH_TIMESTAMP : FWA_TAG_REC_WITHOUT_TIMESTAMP) << 32), 5);
     if (c.with_ts) s.put(5, __builtin_bswap64((uint64_t)(k.win_end[g] - 1)), 8);
     if (c.format == FWA_WIRE_TUPLE) {
+        if constexpr (JS) {                                       // (staged tiles only: COPY)
+            int pos = c.hdr;
+            for (int f = 0; f < c.arity; ++f) {
+                const int t = c.ftype[f];
+                if (t == FWA_FIELD_JSTRING) {
+                    const int64_t so = k.soff[f][g];
+                    const int64_t len = std::max<int64_t>(0, (int64_t)k.soff[f][g + 1] - so);
+                    const int64_t end = (int64_t)k.soff[f][n];
+                    const uint8_t* __restrict__ src = k.sbytes[f] + so;
+                    int nb;
+                    const uint64_t lv = enc_varint((uint64_t)enc_js_chars(src, len, so, end) + 1, &nb);
+                    s.put(pos, lv, nb);
+                    pos += nb;
+                    for (int64_t o = 0; o < len; o += 8)
+                        s.put(pos + (int)o, enc_str_bytes(src + o, (int)std::min<int64_t>(8, len - o), so + o + 8 <= end),
+                              (int)std::min<int64_t>(8, len - o));
+                    pos += (int)len;
+                    continue;
+                }
+                const uint64_t v = enc_load(c, k, f, g);
+                if (t == FWA_FIELD_LONG || t == FWA_FIELD_DOUBLE) { s.put(pos, __builtin_bswap64(v), 8); pos += 8; }
+                else { s.put(pos, __builtin_bswap32((uint32_t)v), 4); pos += 4; }
+            }
+            return;
+        }
         for (int f = 0; f < c.arity; ++f) {
             const uint64_t v = enc_load(c, k, f, g);
             const int t = c.ftype[f];
@@ -203,13 +264,20 @@ __global__ __launch_bounds__(64) void wire_enc_fixed_kernel(EncConst c, EncCols 
 }
 
 // ---- VAR: element sizes ----
-template <bool DEC>
+template <bool DEC, bool JS = false>
 __global__ __launch_bounds__(256) void wire_enc_size_kernel(EncConst c, EncCols k, int64_t n, int64_t* __restrict__ size) {
     for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g <= n; g += (int64_t)gridDim.x * blockDim.x) {
         int64_t s = 0;
         if (g < n) {
             s = c.efix;
             for (int f = 0; f < c.arity; ++f) {
+                if constexpr (JS) {
+                    if (c.ftype[f] != FWA_FIELD_JSTRING) continue;
+                    const int64_t so = k.soff[f][g];
+                    const int64_t len = std::max<int64_t>(0, (int64_t)k.soff[f][g + 1] - so);
+                    s += enc_varint_len((uint64_t)enc_js_chars(k.sbytes[f] + so, len, so, (int64_t)k.soff[f][n]) + 1) + len;
+                    continue;
+                }
                 if (DEC && c.ftype[f] == FWA_FIELD_DECIMAL) {
                     if (!(k.nul[f] && k.nul[f][g])) s += 16;
                     continue;
@@ -224,7 +292,7 @@ __global__ __launch_bounds__(256) void wire_enc_size_kernel(EncConst c, EncCols 
 }
 
 // ---- VAR: the write pass ----
-template <bool DEC>
+template <bool DEC, bool JS = false>
 __global__ __launch_bounds__(64) void wire_enc_var_kernel(EncConst c, EncCols k, int64_t n, const int64_t* __restrict__ eoff,
                                                            uint8_t* __restrict__ out) {
     __shared__ u32x4 buf[(kEncTile + 48) / 16];
@@ -253,7 +321,53 @@ __global__ __launch_bounds__(64) void wire_enc_var_kernel(EncConst c, EncCols k,
             const int nz = (int)((skew + tb + 15) >> 4) + 1;
             for (int i = lane; i < nz; i += 64) buf[i] = z;
             __syncthreads();
-            if (lane < m) enc_element<true, true, DEC>(c, k, g, esize, EncLdsSink{w, (int)epos}, n);
+            if (lane < m) enc_element<true, true, DEC, JS>(c, k, g, esize, EncLdsSink{w, (int)epos}, n);
+        } else if constexpr (JS) {
+            // a run longer than the LDS tile, TUPLE values: field by field, the lanes write their fixed fields and length
+            // prefixes at their running positions, then the wave copies the field's values byte-parallel
+            const EncGlobalSink gs{out + es};
+            int64_t pos = c.hdr;
+            if (lane < m) {
+                gs.put(0, (uint64_t)__builtin_bswap32((uint32_t)(esize - 4)) |
+                              ((uint64_t)(c.with_ts ? FWA_TAG_REC_WITH_TIMESTAMP : FWA_TAG_REC_WITHOUT_TIMESTAMP) << 32), 5);
+                if (c.with_ts) gs.put(5, __builtin_bswap64((uint64_t)(k.win_end[g] - 1)), 8);
+            }
+            for (int f = 0; f < c.arity; ++f) {
+                const int t = c.ftype[f];
+                if (t != FWA_FIELD_JSTRING) {
+                    if (lane < m) {
+                        const uint64_t v = enc_load(c, k, f, g);
+                        if (t == FWA_FIELD_LONG || t == FWA_FIELD_DOUBLE) { gs.put((int)pos, __builtin_bswap64(v), 8); pos += 8; }
+                        else { gs.put((int)pos, __builtin_bswap32((uint32_t)v), 4); pos += 4; }
+                    }
+                    continue;
+                }
+                __syncthreads();                                  // the last field's offsets have been read
+                if (lane < m) {
+                    const int32_t so = k.soff[f][g];
+                    const int64_t len = std::max<int64_t>(0, (int64_t)k.soff[f][g + 1] - so);
+                    int nb;
+                    const uint64_t lv = enc_varint((uint64_t)enc_js_chars(k.sbytes[f] + so, len, so, (int64_t)k.soff[f][n]) + 1, &nb);
+                    gs.put((int)pos, lv, nb);
+                    pos += nb;
+                    s_so[lane] = so;
+                    s_dst[lane] = es + pos;
+                    pos += len;
+                }
+                if (lane == 0) s_so[m] = k.soff[f][base + m];
+                __syncthreads();
+                const int32_t o0 = s_so[0], total = s_so[m] - o0;
+                const uint8_t* __restrict__ src = k.sbytes[f];
+                for (int32_t j = lane; j < total; j += 64) {
+                    const int32_t tt = o0 + j;
+                    int lo = 0, hi = m;                           // last row with offset <= tt (skips empty values)
+                    while (hi - lo > 1) {
+                        const int mid = (lo + hi) >> 1;
+                        if (s_so[mid] <= tt) lo = mid; else hi = mid;
+                    }
+                    out[s_dst[lo] + (tt - s_so[lo])] = src[tt];
+                }
+            }
         } else {
             // a run longer than the LDS tile: everything but the values' bytes by the row's lane, then those bytes field by
             // field (their variable-length parts follow in field order, the 16 bytes of a DECIMAL, already written, among
@@ -418,13 +532,17 @@ int fwa_wire_enc_create(const fwa_wire_out_schema* s, fwa_wire_encoder** out) {
     c.hdr = c.with_ts ? 13 : 5;
     c.nullbits = ((s->arity + 63 + 8) / 64) * 8;                  // BinaryRowData.calculateBitSetWidthInBytes
     c.row_size = c.nullbits + 8 * s->arity;
-    static const char* tname[] = {"LONG", "DOUBLE", "FLOAT", "INT", "STRING", "?", "DECIMAL"};
+    static const char* tname[] = {"LONG", "DOUBLE", "FLOAT", "INT", "STRING", "?", "DECIMAL", "?", "JSTRING"};
     static const char* cname[] = {"an int64", "an int32", "a double", "a float", "a STRING", "a DECIMAL"};
     int off = c.hdr;
     for (int f = 0; f < s->arity; ++f) {
         const int t = s->field[f];
         const std::string at = "field " + std::to_string(f) + ": ";
-        if (t < FWA_FIELD_LONG || (t > FWA_FIELD_STRING && t != FWA_FIELD_DECIMAL)) return bad(FWA_E_ARG, at + "unknown field type");
+        if (t < FWA_FIELD_LONG || (t > FWA_FIELD_STRING && t != FWA_FIELD_DECIMAL && t != FWA_FIELD_JSTRING))
+            return bad(FWA_E_ARG, at + "unknown field type");
+        if (t == FWA_FIELD_JSTRING && s->format != FWA_WIRE_TUPLE)
+            return bad(FWA_E_ARG, at + "JSTRING fields (StringSerializer) are written in TUPLE values only: a row's CHAR / "
+                                       "VARCHAR / STRING field is STRING");
         if (t == FWA_FIELD_DECIMAL && s->format != FWA_WIRE_ROWDATA)
             return bad(FWA_E_ARG, at + "DECIMAL fields are written in ROWDATA rows only (a Tuple's BigDecSerializer is another "
                                        "format)");
@@ -462,7 +580,7 @@ int fwa_wire_enc_create(const fwa_wire_out_schema* s, fwa_wire_encoder** out) {
             case kEncF64: ok = t == FWA_FIELD_DOUBLE; break;
             case kEncF32: ok = t == FWA_FIELD_FLOAT; break;
             case kEncDec: ok = t == FWA_FIELD_DECIMAL; break;
-            default: ok = t == FWA_FIELD_STRING; break;
+            default: ok = t == FWA_FIELD_STRING || t == FWA_FIELD_JSTRING; break;   // (each in its own format, above)
         }
         if (!ok) return bad(FWA_E_ARG, at + cname[cls] + " source cannot be written as " + tname[t]);
         c.ftype[f] = t;
@@ -470,7 +588,8 @@ int fwa_wire_enc_create(const fwa_wire_out_schema* s, fwa_wire_encoder** out) {
         c.adj[f] = s->src[f] == FWA_SRC_WIN_TIME ? -1 : 0;
         if (t == FWA_FIELD_STRING) ++c.nstr;
         if (t == FWA_FIELD_DECIMAL) ++c.ndec;
-        if (s->format == FWA_WIRE_TUPLE) { c.foff[f] = off; off += field_bytes(t); }
+        if (t == FWA_FIELD_JSTRING) ++c.njs;
+        if (s->format == FWA_WIRE_TUPLE) { c.foff[f] = off; off += t == FWA_FIELD_JSTRING ? 0 : field_bytes(t); }
         else c.foff[f] = c.hdr + 4 + c.nullbits + 8 * f;
     }
     c.efix = s->format == FWA_WIRE_TUPLE ? off : c.hdr + 4 + c.row_size;
@@ -585,8 +704,8 @@ int fwa_wire_encode(fwa_wire_encoder* e, const fwa_out* rows, const fwa_wire_key
             at += (x.bytes + 15) & ~15ll;
         }
     }
-    const bool var = c.nstr + c.ndec > 0;
-    const bool dec = c.ndec > 0;
+    const bool var = c.nstr + c.ndec + c.njs > 0;
+    const bool dec = c.ndec > 0, js = c.njs > 0;
     int64_t rows_bytes = n * c.efix;
     float ms_size = 0, ms_scan = 0, ms_write = 0;
     const unsigned grid = (unsigned)std::min<int64_t>((n + 63) / 64, kEncBlocks);
@@ -603,7 +722,8 @@ int fwa_wire_encode(fwa_wire_encoder* e, const fwa_out* rows, const fwa_wire_key
         }
         ECK(hipEventRecord(e->ev[0], st));
         const dim3 sgrid((unsigned)std::min<int64_t>((n + 256) / 256, 4096));
-        if (dec) hipLaunchKernelGGL(wire_enc_size_kernel<true>, sgrid, dim3(256), 0, st, c, k, n, e->d_size);
+        if (js) hipLaunchKernelGGL((wire_enc_size_kernel<false, true>), sgrid, dim3(256), 0, st, c, k, n, e->d_size);
+        else if (dec) hipLaunchKernelGGL(wire_enc_size_kernel<true>, sgrid, dim3(256), 0, st, c, k, n, e->d_size);
         else hipLaunchKernelGGL(wire_enc_size_kernel<false>, sgrid, dim3(256), 0, st, c, k, n, e->d_size);
         ECK(hipGetLastError());
         ECK(hipEventRecord(e->ev[1], st));
@@ -628,7 +748,8 @@ int fwa_wire_encode(fwa_wire_encoder* e, const fwa_out* rows, const fwa_wire_key
     if (int rc = egrow(e, &e->d_out, &e->out_cap, nbytes + 16)) return rc;
     if (n > 0) {
         ECK(hipEventRecord(e->ev[3], st));
-        if (dec) hipLaunchKernelGGL(wire_enc_var_kernel<true>, dim3(grid), dim3(64), 0, st, c, k, n, e->d_off, e->d_out);
+        if (js) hipLaunchKernelGGL((wire_enc_var_kernel<false, true>), dim3(grid), dim3(64), 0, st, c, k, n, e->d_off, e->d_out);
+        else if (dec) hipLaunchKernelGGL(wire_enc_var_kernel<true>, dim3(grid), dim3(64), 0, st, c, k, n, e->d_off, e->d_out);
         else if (var) hipLaunchKernelGGL(wire_enc_var_kernel<false>, dim3(grid), dim3(64), 0, st, c, k, n, e->d_off, e->d_out);
         else hipLaunchKernelGGL(wire_enc_fixed_kernel, dim3(grid), dim3(64), (size_t)(64 * c.efix + 32), st, c, k, n, e->d_out);
         ECK(hipGetLastError());

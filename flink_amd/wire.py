@@ -19,6 +19,13 @@ DECIMAL fields (precision > 18, non-compact, ROWDATA rows) decode to int64 [n, 2
 `_abi.dec128_column` makes and SUM_DEC128 / AVG_DEC128 read -- and the DECIMAL aggregates' results are written as
 "DECIMAL" fields by the encoder. A DECIMAL with precision <= 18 is its unscaled long: "LONG" in both directions.
 
+JSTRING fields (java.lang.String fields of TUPLE values, StringSerializer's varint-prefixed UTF-16 code units) come back
+through `DecodedBatch.strings(f)` too, as their canonical char bytes (the bytes behind the length prefix, as they stand
+on the wire; `jstring_text` / `jstring_bytes` convert for display). `NetworkInput(schema, engine, keydict=d, key_string=f)`
+runs a String-keyed DataStream job from the channel's bytes: ids from `d.encode`, `String.hashCode()` from `jstring_hash`,
+both on the device, pushed into a KEY_PREHASHED handle. A dictionary holding such values must not also be fed UTF-8
+"STRING" values: the same non-ASCII text has different bytes in the two forms.
+
 The other direction: `WireEncoder` binds fwa_wire_encode -- the SoA columns of a watermark step (fwa_out, and the decoded
 key dictionary columns of a Table job) become the bytes RecordWriter would have produced, in HBM -- and `NetworkOutput`
 is the mirror of RecordWriterOutput (flink-streaming-java/.../runtime/io/RecordWriterOutput.java:131-135 and its
@@ -35,7 +42,7 @@ from .keydict import FIELD as KEY_FIELD, KeyStrings
 
 MAX_FIELDS = 16
 FORMATS = {"TUPLE": 0, "ROWDATA": 1}
-FIELDS = {"LONG": 0, "DOUBLE": 1, "FLOAT": 2, "INT": 3, "STRING": 4, "DECIMAL": 6}   # (5 is unassigned)
+FIELDS = {"LONG": 0, "DOUBLE": 1, "FLOAT": 2, "INT": 3, "STRING": 4, "DECIMAL": 6, "JSTRING": 8}   # (5, 7 are unassigned)
 FIELD_DTYPE = {0: "i8", 1: "f8", 2: "f4", 3: "i8", 6: "i8"}  # value-column dtype per field type (DECIMAL: two per record)
 TAG_REC_WITH_TIMESTAMP, TAG_REC_WITHOUT_TIMESTAMP, TAG_WATERMARK, TAG_LATENCY_MARKER, TAG_STREAM_STATUS, \
     TAG_RECORD_ATTRIBUTES = range(6)
@@ -65,8 +72,9 @@ class WireStats(C.Structure):
 
 
 def make_schema(fields, key_field, ts_field=-1, cols=(), fmt="TUPLE", device=0, max_bytes=0):
-    """fields: field type names in value order ("LONG", "DOUBLE", "FLOAT", "INT", and "STRING" / "DECIMAL" in ROWDATA rows);
-    key_field -1 (schemas with a STRING field) = the caller builds the key; ts_field -1 = the StreamRecord
+    """fields: field type names in value order ("LONG", "DOUBLE", "FLOAT", "INT", "STRING" / "DECIMAL" in ROWDATA rows and
+    "JSTRING", a java.lang.String, in TUPLE values); key_field -1 (schemas with a STRING field; always with a JSTRING
+    field) = the caller builds the key; ts_field -1 = the StreamRecord
     timestamp; cols: the fields that become value columns 0, 1, ..."""
     s = Schema()
     s.format = FORMATS[fmt]
@@ -79,6 +87,82 @@ def make_schema(fields, key_field, ts_field=-1, cols=(), fmt="TUPLE", device=0, 
         s.col_field[j] = f
     s.device, s.max_bytes = device, max_bytes
     return s
+
+
+def jstring_bytes(text):
+    """The canonical char bytes of a String (StringValue.writeString's coding of each UTF-16 code unit, 1..3 bytes,
+    without the length prefix): what DecodedBatch.strings returns for a JSTRING field and what a key dictionary of
+    String keys holds. Lone surrogates are code units like any other."""
+    raw = text.encode("utf-16-le", "surrogatepass")
+    out = bytearray()
+    for i in range(0, len(raw), 2):
+        c = raw[i] | (raw[i + 1] << 8)
+        while c >= 0x80:
+            out.append((c & 0x7F) | 0x80)
+            c >>= 7
+        out.append(c)
+    return bytes(out)
+
+
+def jstring_text(data):
+    """The String of canonical char bytes (the inverse of jstring_bytes)."""
+    units = bytearray()
+    c = sh = 0
+    for b in bytes(data):
+        c |= (b & 0x7F) << sh
+        sh += 7
+        if b < 0x80:
+            if c > 0xFFFF or sh > 21 or (sh > 7 and b == 0):
+                raise ValueError("not the canonical coding of a UTF-16 code unit")
+            units += bytes((c & 0xFF, c >> 8))
+            c = sh = 0
+    if sh:
+        raise ValueError("the bytes end inside a char")
+    return bytes(units).decode("utf-16-le", "surrogatepass")
+
+
+def jstring_field(text):
+    """The field bytes StringSerializer writes: the varint of len + 1 (UTF-16 code units), then the chars; None is 00."""
+    if text is None:
+        return b"\x00"
+    body = jstring_bytes(text)
+    n = sum(1 for b in body if b < 0x80) + 1
+    out = bytearray()
+    while n >= 0x80:
+        out.append((n & 0x7F) | 0x80)
+        n >>= 7
+    out.append(n)
+    return bytes(out) + body
+
+
+def jstring_hash(offsets, data, nulls=None):
+    """String.hashCode() of values in the canonical char-byte form, on the device: offsets int32 [n + 1] (they need not
+    start at 0), data uint8, nulls uint8 [n] or None (a NULL value hashes to 0), all torch CUDA tensors. Returns a torch
+    int32 CUDA tensor [n]: the key_hash column of WindowAggregator.push on a KEY_PREHASHED handle."""
+    import torch
+    for t in (offsets, data) + (() if nulls is None else (nulls,)):
+        if not _is_torch_cuda(t):
+            raise EngineError(-1, "jstring_hash takes CUDA tensors")
+    if offsets.dtype != torch.int32 or data.dtype != torch.uint8:
+        raise EngineError(-1, "jstring_hash: offsets are int32 and data uint8")
+    offsets, data = offsets.contiguous(), data.contiguous()
+    n = offsets.numel() - 1
+    if n < 0:
+        raise EngineError(-1, "jstring_hash: offsets has n + 1 entries")
+    if nulls is not None:
+        nulls = nulls.contiguous()
+        if nulls.dtype == torch.bool:
+            nulls = nulls.view(torch.uint8)
+        if nulls.dtype != torch.uint8 or nulls.numel() != n:
+            raise EngineError(-1, "jstring_hash: nulls is uint8 [n]")
+    L = _bind(lib())
+    out = torch.empty(n, dtype=torch.int32, device=offsets.device)
+    torch.cuda.synchronize()
+    rc = L.fwa_jstring_hash(offsets.data_ptr(), data.data_ptr(), None if nulls is None else nulls.data_ptr(), n,
+                            out.data_ptr(), offsets.device.index or 0)
+    if rc:
+        raise EngineError(rc, "fwa_jstring_hash")
+    return out
 
 
 def _bind(L):
@@ -96,6 +180,8 @@ def _bind(L):
     L.fwa_wire_get_stats.restype = C.c_int
     L.fwa_wire_strings_of.argtypes = [C.c_void_p, C.c_int32, C.POINTER(Strings)]
     L.fwa_wire_strings_of.restype = C.c_int
+    L.fwa_jstring_hash.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32]
+    L.fwa_jstring_hash.restype = C.c_int
     L._wire_bound = True
     return L
 
@@ -130,7 +216,7 @@ class DecodedBatch:
             self.evt_val = np.zeros((0, 4), np.int64)
 
     def strings(self, f):
-        """(offsets int32 [n + 1], bytes uint8, null uint8 [n]) of STRING field f: views valid until the decoder's
+        """(offsets int32 [n + 1], bytes uint8, null uint8 [n]) of STRING or JSTRING field f (a JSTRING's canonical char bytes): views valid until the decoder's
         next decode. (offsets[a:b + 1], bytes) is what KeyDictionary.encode takes for records [a, b). Device input
         of the decode must still be alive and unchanged at the first call per field (the extraction is lazy)."""
         return self._decoder.strings_of(f, self.n_records)
@@ -198,13 +284,32 @@ class NetworkInput:
     buffer is carried over (SpanningWrapper). Returns the window rows fired by the watermarks in it.
     """
 
-    def __init__(self, schema, engine, keydict=None, key_parts=None):
+    def __init__(self, schema, engine, keydict=None, key_parts=None, key_string=None):
         """keydict (flink_amd.keydict.KeyDictionary) with key_parts, the key row's fields in the dictionary's order,
         each ("str", field) -- a STRING field of the schema -- or ("col", j) -- value column j: every run of records
         is pushed under the ids keydict.encode gives its key rows (NULL flags included; a NULL grouping key is a
-        key like any other there). Without keydict the schema's key_field is the key, as before."""
-        if (keydict is None) != (key_parts is None):
+        key like any other there). Without keydict the schema's key_field is the key, as before.
+        keydict with key_string=f, a JSTRING field of a TUPLE schema: a DataStream job keyed by that String. keydict is a
+        one-field STRING dictionary (it holds the keys' canonical char bytes) and engine a KEY_PREHASHED handle; every
+        run of records is pushed under keydict.encode's ids with key_hash = jstring_hash(...), String.hashCode() computed
+        on the device, so the handle's key-group check reads the hash Flink's would. A null key raises
+        EngineError(-1, "Assigned key must not be null") like KeyGroupRangeAssignment.assignToKeyGroup."""
+        if key_string is not None:
+            if key_parts is not None:
+                raise EngineError(-1, "key_string and key_parts exclude each other: a String key is one JSTRING field")
+            if keydict is None:
+                raise EngineError(-1, "key_string needs keydict, a one-field STRING KeyDictionary")
+            if list(keydict.types) != [KEY_FIELD["STRING"]]:
+                raise EngineError(-1, "key_string: the key dictionary has exactly one field, a STRING")
+            key_string = int(key_string)
+            if not (schema.format == FORMATS["TUPLE"] and 0 <= key_string < schema.arity
+                    and schema.field[key_string] == FIELDS["JSTRING"]):
+                raise EngineError(-1, "key_string names a JSTRING field of a TUPLE schema")
+            if engine.cfg.key_kind != A.KEY_PREHASHED:
+                raise EngineError(-1, "key_string needs a KEY_PREHASHED handle: the ids go beside String.hashCode()")
+        elif (keydict is None) != (key_parts is None):
             raise EngineError(-1, "keydict and key_parts go together")
+        self.key_string = key_string
         self.decoder = WireDecoder(schema)
         self.engine = engine
         self.keydict = keydict
@@ -222,6 +327,8 @@ class NetworkInput:
     def _push(self, batch, a, b):
         if b <= a:
             return
+        if getattr(self, "key_string", None) is not None:
+            return self._push_string(batch, a, b)
         if getattr(self, "keydict", None) is not None:
             return self._push_dict(batch, a, b)
         if batch.key_null is not None and bool(batch.key_null[a:b].any()):
@@ -248,6 +355,16 @@ class NetworkInput:
         if batch.col_null is not None and self.engine.cfg.nullable_cols:
             vn = [c[a:b] for c in batch.col_null]
         self.late_dropped += self.engine.push(ids, batch.ts[a:b], [c[a:b] for c in batch.cols], nulls=vn)
+        self.records_in += b - a
+
+    def _push_string(self, batch, a, b):
+        offs, data, nul = batch.strings(self.key_string)
+        if bool(nul[a:b].any()):
+            raise EngineError(-1, "Assigned key must not be null")   # KeyGroupRangeAssignment.assignToKeyGroup
+        run = offs[a:b + 1]                                      # offsets need not start at 0
+        ids = self.keydict.encode([(run, data)])
+        self.late_dropped += self.engine.push(ids, batch.ts[a:b], [c[a:b] for c in batch.cols],
+                                              key_hash=jstring_hash(run, data))
         self.records_in += b - a
 
     def feed(self, buffer):
@@ -320,8 +437,9 @@ class EncStats(C.Structure):                # fwa_wire_enc_stats
 
 
 def make_out_schema(fields, fmt="TUPLE", record_ts=None, device=0, max_bytes=0):
-    """fields, in the value's order: (wire type, source) pairs. The wire type is "LONG" / "DOUBLE" / "FLOAT" / "INT", or
-    "STRING" / "DECIMAL" in ROWDATA rows; the source is "KEY", "WIN_START", "WIN_END", "WIN_TIME" (win_end - 1),
+    """fields, in the value's order: (wire type, source) pairs. The wire type is "LONG" / "DOUBLE" / "FLOAT" / "INT",
+    "STRING" / "DECIMAL" in ROWDATA rows, or "JSTRING" in TUPLE values (a java.lang.String; its one source is
+    ("KEYCOL", k, "STRING"), the dictionary-decoded key in the canonical char-byte form); the source is "KEY", "WIN_START", "WIN_END", "WIN_TIME" (win_end - 1),
     ("AGG", j, kind) with the aggregate's kind name as in flink_amd._abi.AGG_KINDS (it fixes the dtype of the result
     column), or ("KEYCOL", k, type) with the key dictionary column's type ("BIGINT" / "INT" / "DOUBLE" / "STRING").
     "DECIMAL" takes exactly the DECIMAL aggregates ("SUM_DEC" / "AVG_DEC" / "SUM_DEC128" / "AVG_DEC128": a DECIMAL(38, s)).
@@ -490,6 +608,11 @@ class NetworkOutput:
                 i8 = np.dtype("i8")
                 ids = dev_view(out.key, n, i8) if out.on_device else _host_to_np(out.key, n, i8)
                 kc = self.keydict.decode_device(ids)
+                if self.encoder.schema.format == FORMATS["TUPLE"]:   # TupleSerializer cannot write null fields
+                    import torch
+                    if bool(torch.stack(kc[1]).any()):
+                        raise EngineError(-1, "a NULL key column in a TUPLE value: TupleSerializer cannot write null fields")
+                    kc = (kc[0], None)
             else:
                 kc = self._no_rows()[1]
         self.rows_out += n

@@ -48,11 +48,29 @@
  * first. A decoded DECIMAL column is 16-byte little-endian two's complement values, the input of FWA_SUM_DEC128 /
  * FWA_AVG_DEC128; the 38-digit bound is theirs to apply, not the decoder's.
  *
+ * In TUPLE values a java.lang.String field is FWA_FIELD_JSTRING (StringSerializer.serialize -> StringValue.writeString,
+ * read back by StringValue.readString; flink-core/.../types/StringValue.java): len + 1 in 7-bit groups, low group first,
+ * every group but the last with bit 7 set (len = the number of UTF-16 code units), then each code unit coded the same
+ * way -- 1 to 3 bytes, a third byte at most 0x03. A null String is the single byte 00. Nothing is aligned or padded:
+ * the fields behind a String start where it ended. "key1" is 05 6b 65 79 31, "" is 01, U+FFFF is 02 ff ff 03.
+ * The canonical form of a value is its char bytes exactly as they stand on the wire (the bytes behind the length
+ * prefix): that is what fwa_wire_strings_of returns, what the key dictionary stores and what the encoder writes back
+ * behind a new prefix. For ASCII it is the text itself. Every Flink writer produces the shortest coding of a char, so
+ * two Strings are equal iff these bytes are equal (the dictionary's byte equality needs exactly that), the code-unit
+ * count is the number of bytes below 0x80, nothing is transcoded in either direction and lone surrogates survive.
+ * A key dictionary must not mix these values with UTF-8 FWA_FIELD_STRING values: the same non-ASCII text has different
+ * bytes in the two forms. Stated deviation: the reference reader accepts a non-canonical char (more than 3 groups, a
+ * value above 0xFFFF, a multi-byte char whose last group is zero) and truncates it with (char); the decoder answers
+ * FWA_E_CORRUPT, since no writer produces such bytes and accepting them would make byte equality differ from String
+ * equality. A length prefix of several groups whose value is 0 (80 00; the reference reader would ask for a char[-1])
+ * is FWA_E_CORRUPT as well. A schema with a JSTRING field has key_field -1; a DataStream String key goes to a
+ * FWA_KEY_PREHASHED handle as fwa_keydict_encode ids beside fwa_jstring_hash hashes, both computed on the device.
+ *
  * Limits. An element (tag byte to its last byte; the 4-byte length prefix's value) may be at most 249 bytes: the
  * boundary maps keep entry offsets in a byte. A longer record ends the call with FWA_E_UNSUPPORTED and its byte
  * position, never FWA_E_CORRUPT; raising the ceiling needs 16-bit entry offsets in the maps and is a follow-up.
- * Not supported (FWA_E_UNSUPPORTED): STRING fields of TUPLE values (StringSerializer writes varint-prefixed UTF-16
- * code units, and DataStream String keys are FWA_KEY_PREHASHED), non-INSERT RowKinds, LZ4-compressed buffers
+ * Not supported (FWA_E_UNSUPPORTED): FWA_FIELD_STRING in TUPLE values (a Tuple's String is FWA_FIELD_JSTRING) and
+ * FWA_FIELD_JSTRING in ROWDATA rows, String fields as value columns or as key_field, non-INSERT RowKinds, LZ4-compressed buffers
  * (taskmanager.network.compression), DECIMAL fields of TUPLE values (BigDecSerializer is another format) or as key
  * dictionary columns, and the other variable-length SQL types (TIMESTAMP with p > 3). Status codes:
  * include/flink_amd.h.
@@ -92,10 +110,12 @@ enum fwa_wire_format {
  * ts_field or a col_field (FWA_E_ARG); with FWA_WIRE_TUPLE it is FWA_E_UNSUPPORTED. A DECIMAL field may be a col_field
  * (or be read by no column: it is skipped); as key_field or ts_field it is FWA_E_ARG, with FWA_WIRE_TUPLE
  * FWA_E_UNSUPPORTED. Value 5 is unassigned and stays refused (FWA_E_UNSUPPORTED by the decoder, FWA_E_ARG by the
- * encoder), like every other unknown value. */
+ * encoder), like every other unknown value, and so does 7. A JSTRING field (java.lang.String of a FWA_WIRE_TUPLE value;
+ * any number of them, at any position) cannot be key_field, ts_field or a col_field (FWA_E_ARG), its schema has
+ * key_field -1 (FWA_E_ARG otherwise; batch.key / key_null are NULL), and with FWA_WIRE_ROWDATA it is FWA_E_UNSUPPORTED. */
 enum fwa_wire_field {
     FWA_FIELD_LONG = 0, FWA_FIELD_DOUBLE = 1, FWA_FIELD_FLOAT = 2, FWA_FIELD_INT = 3, FWA_FIELD_STRING = 4,
-    FWA_FIELD_DECIMAL = 6
+    FWA_FIELD_DECIMAL = 6, FWA_FIELD_JSTRING = 8
 };
 
 typedef struct fwa_wire_schema {
@@ -152,7 +172,8 @@ const char* fwa_wire_last_error(const fwa_wire_decoder* d);
  * element boundary). Device bytes (FWA_WIRE_DEVICE_BYTES) must be complete when the call is made: the decoder
  * runs on its own stream (the caller synchronises the producer's stream first); everything is complete on
  * return. A malformed element (unknown tag, a length that does not match its tag and the schema, a row size int
- * that differs from the element's length, a STRING slot pointing outside its row, or the slot of a non-NULL DECIMAL
+ * that differs from the element's length, a STRING slot pointing outside its row, a TUPLE value with JSTRING fields
+ * whose field walk does not end exactly at the element's end or meets a non-canonical char, or the slot of a non-NULL DECIMAL
  * column whose bytes lie outside the row's variable-length part or number 0 or more than 16) returns
  * FWA_E_CORRUPT ("Corrupt stream, found tag", StreamElementSerializer.java:208-210).
  * Device timing of the decode kernels accumulates in fwa_wire_stats. */
@@ -169,7 +190,7 @@ typedef struct fwa_wire_stats {
 
 int fwa_wire_get_stats(fwa_wire_decoder* d, fwa_wire_stats* out);
 
-/* The values of STRING field `field` in the records of the last fwa_wire_decode, in record order: exactly what
+/* The values of STRING or JSTRING field `field` (a JSTRING's canonical char bytes) in the records of the last fwa_wire_decode, in record order: exactly what
  * fwa_key_strings takes ({offsets + a, bytes} are records [a, b) for fwa_keydict_encode, no copy). Decoder-owned,
  * valid until the next call of fwa_wire_decode on it. A NULL field has length 0 and null = 1.
  * The extraction is lazy (a device scan of the lengths, then a gather from the wire bytes), so those bytes must
@@ -184,6 +205,13 @@ typedef struct fwa_wire_strings {
     int64_t total_bytes;
 } fwa_wire_strings;
 int fwa_wire_strings_of(fwa_wire_decoder* d, int32_t field, fwa_wire_strings* out);
+
+/* String.hashCode() (s[0]*31^(n-1) + ... + s[n-1] over UTF-16 code units, int wrap-around) of n values in the
+ * canonical char-byte form, device pointers, Arrow offsets that need not start at 0; nulls may be NULL; a NULL
+ * value hashes to 0. The key_hash column of fwa_push for FWA_KEY_PREHASHED; the counterpart of fwa_binrow_hash.
+ * Runs on the device's default stream and is complete on return. */
+int fwa_jstring_hash(const int32_t* offsets, const uint8_t* bytes, const uint8_t* nulls, int64_t n,
+                     int32_t* out, int32_t device);
 
 /* ---- wire encoder: fired rows written as channel bytes on the GPU ----
  *
@@ -209,8 +237,11 @@ int fwa_wire_strings_of(fwa_wire_decoder* d, int32_t field, fwa_wire_strings* ou
  * (AbstractStreamOperator.processWatermark :610-615). Cutting the bytes into 32 KiB network buffers stays with the
  * caller; elements span buffers freely. The GPU decoder above is a receiver of these bytes.
  *
- * Limits. arity 1..FWA_WIRE_MAX_FIELDS; KEYCOL index < FWA_KEYDICT_MAX_ARITY; STRING fields in ROWDATA rows only
- * (FWA_E_ARG); a TUPLE value cannot carry NULLs (FWA_E_ARG at encode when a source has NULL flags). The DECIMAL
+ * Limits. arity 1..FWA_WIRE_MAX_FIELDS; KEYCOL index < FWA_KEYDICT_MAX_ARITY; STRING fields in ROWDATA rows only and
+ * JSTRING fields in TUPLE values only (FWA_E_ARG). A JSTRING field takes one source, a FWA_SRC_KEYCOL column of type
+ * FWA_KEY_FIELD_STRING holding values in the canonical char-byte form (the dictionary-decoded keys of a job fed by the
+ * decoder above): the varint of (count of bytes below 0x80) + 1, then the bytes verbatim, the fields behind it
+ * unaligned; a TUPLE value cannot carry NULLs (FWA_E_ARG at encode when a source has NULL flags). The DECIMAL
  * aggregates (FWA_SUM_DEC / FWA_AVG_DEC / FWA_SUM_DEC128 / FWA_AVG_DEC128: every result is a DECIMAL(38, s), 16 bytes
  * per row in fwa_out) are written as FWA_FIELD_DECIMAL only, in ROWDATA rows: the minimal unscaled bytes in 16 reserved
  * ones, a NULL result (agg_null) as setNullAt, the form RowDataSerializer.toBinaryRow :196-212 gives the operator's
@@ -238,7 +269,7 @@ enum fwa_wire_record_ts {
  * window properties as the query does.
  * Allowed source -> wire type pairs (anything else is FWA_E_ARG at create): an int64 column -> LONG, or INT (the low
  * 32 bits, Java's narrowing cast); an int32 column -> INT, or LONG (sign-extended); double -> DOUBLE; float -> FLOAT;
- * a key dictionary STRING column -> STRING; a DECIMAL aggregate (FWA_SRC_AGG with src_kind FWA_SUM_DEC .. FWA_AVG_DEC128,
+ * a key dictionary STRING column -> STRING (ROWDATA) or JSTRING (TUPLE); a DECIMAL aggregate (FWA_SRC_AGG with src_kind FWA_SUM_DEC .. FWA_AVG_DEC128,
  * 14..17) -> DECIMAL and nothing else. FWA_FIRST_64 / FWA_SEL_64 hold a field's raw bits and also go out as DOUBLE,
  * FWA_FIRST_32 / FWA_SEL_32 also as FLOAT. */
 typedef struct fwa_wire_out_schema {
@@ -289,7 +320,8 @@ typedef struct fwa_wire_bytes {
 
 typedef struct fwa_wire_encoder fwa_wire_encoder;
 
-/* FWA_E_ARG: unknown format / field / source, arity or an index out of range, STRING or DECIMAL in a TUPLE value, a
+/* FWA_E_ARG: unknown format / field / source, arity or an index out of range, STRING or DECIMAL in a TUPLE value,
+ * JSTRING in a ROWDATA row or over any source but a key dictionary STRING column, a
  * source -> wire type pair that is not allowed. FWA_E_UNSUPPORTED: a DECIMAL aggregate source under a wire type other
  * than FWA_FIELD_DECIMAL. FWA_E_DEVICE / FWA_E_OOM: HIP.
  * fwa_wire_enc_last_error(NULL) says why a create failed (per thread). */
