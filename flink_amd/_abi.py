@@ -88,7 +88,7 @@ def dec128_values(raw):
     return out
 
 STATUS = {0: "OK", -1: "E_ARG", -2: "E_TS_MIN", -3: "E_KEYGROUP", -4: "E_MERGE_LATE", -5: "E_OOM",
-          -6: "E_DEVICE", -7: "E_UNSUPPORTED", -8: "E_STATE", -9: "E_CORRUPT"}
+          -6: "E_DEVICE", -7: "E_UNSUPPORTED", -8: "E_STATE", -9: "E_CORRUPT", -10: "E_INTERNAL"}
 
 CFG_DYNAMIC_GAP = 0x1
 CFG_LATE_INDICES = 0x2
@@ -97,6 +97,7 @@ CFG_REDUCE = 0x8
 CFG_BY_LAST = 0x10
 CFG_DISTINCT_RANGE = 0x20
 CFG_DISTINCT_SESSION = 0x40
+CFG_F32_FOLD = 0x80
 
 PUSH_DEVICE_PTRS = 0x1
 PUSH_ASYNC = 0x2
@@ -174,14 +175,15 @@ def make_config(window_kind="TUMBLE", semantics="DATASTREAM", size_ms=10_000, sl
                 key_kind=KEY_JAVA_LONG, max_parallelism=128, kg_start=0, kg_end=None, device=0,
                 output_on_device=0, key_capacity=0, max_batch=0, gap_col=None, tz=None, late_indices=False,
                 nullable_cols=(), record_lists=False, reduce=False, by_last=False, distinct_range=False,
-                distinct_session=False):
+                distinct_session=False, f32_fold=False):
     """Build a Config struct. aggs: sequence of (agg name, value-column index). gap_col: value column of
     per-record session gaps (DynamicEventTimeSessionWindows). tz: [(utc_instant_ms, offset_ms), ...] shift
     time zone of a TIMESTAMP_LTZ rowtime (the struct keeps a pointer to a buffer held on the struct). reduce: a
     DataStream built-in reduction (FWA_CFG_REDUCE, WindowedStream.sum/min/max/minBy/maxBy); by_last: minBy / maxBy
     ties go to the last element (FWA_CFG_BY_LAST). distinct_range: allow COUNT_DISTINCT and SUM / AVG_DISTINCT_* on a
     Table HOP / CUMULATE handle, taken from the set at every fire (FWA_CFG_DISTINCT_RANGE). distinct_session: the same
-    aggregates on a Table SESSION handle with a fixed gap (FWA_CFG_DISTINCT_SESSION)."""
+    aggregates on a Table SESSION handle with a fixed gap (FWA_CFG_DISTINCT_SESSION). f32_fold: every SUM_F32 of a
+    TUMBLE handle is the reference's float32 arrival-order fold, bit for bit (FWA_CFG_F32_FOLD)."""
     c = Config()
     c.abi_version = FWA_ABI_VERSION
     c.window_kind = WINDOW_KINDS[window_kind] if isinstance(window_kind, str) else int(window_kind)
@@ -217,6 +219,8 @@ def make_config(window_kind="TUMBLE", semantics="DATASTREAM", size_ms=10_000, sl
         c.flags |= CFG_DISTINCT_RANGE
     if distinct_session:
         c.flags |= CFG_DISTINCT_SESSION
+    if f32_fold:
+        c.flags |= CFG_F32_FOLD
     for col in nullable_cols:                             # value columns that may hold SQL NULLs
         c.nullable_cols |= 1 << col
     if gap_col is not None:

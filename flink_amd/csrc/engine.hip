@@ -1021,11 +1021,13 @@ int64_t gcd64(int64_t a, int64_t b) {
 struct SpState;                       // record-list window state (sparse.inc)
 struct DecPlan;                       // DECIMAL aggregates over 32-bit piece sums (decimal.inc)
 struct DistinctPlan;                  // COUNT(DISTINCT) over a marked 0/1 column and a device-resident set (distinct.inc)
+struct FoldPlan;                      // SUM(FLOAT) as a float32 arrival-order fold, FWA_CFG_F32_FOLD (f32fold.inc)
 
 struct fwa_engine {
     fwa_config cfg;                   // the engine's configuration (DECIMAL handles: the internal one, see decimal.inc)
     DecPlan* dec = nullptr;
     DistinctPlan* dist = nullptr;     // COUNT(DISTINCT) handles: cfg is the internal configuration too (distinct.inc)
+    FoldPlan* fold = nullptr;         // FWA_CFG_F32_FOLD handles with a SUM_F32 aggregate (f32fold.inc)
     const void* dev_override[FWA_MAX_COLS] = {};   // stage_inputs: value columns already on the device
     bool restoring = false;           // fwa_restore feeding fwa_push_partials
     // FWA_KEY_PREHASHED: the caller's key.hashCode() of every key, by kid (the key table's slot), so a snapshot can
@@ -1329,7 +1331,7 @@ int validate(const fwa_config* c) {
             return FWA_E_ARG;
     }
     if (c->flags & ~(FWA_CFG_DYNAMIC_GAP | FWA_CFG_LATE_INDICES | FWA_CFG_RECORD_LISTS | FWA_CFG_REDUCE | FWA_CFG_BY_LAST |
-                     FWA_CFG_DISTINCT_RANGE | FWA_CFG_DISTINCT_SESSION))
+                     FWA_CFG_DISTINCT_RANGE | FWA_CFG_DISTINCT_SESSION | FWA_CFG_F32_FOLD))
         return FWA_E_ARG;
     {   // DataStream built-in reductions (include/flink_amd.h FWA_CFG_REDUCE)
         int nby = 0, nsel = 0, nfirst = 0, nred = 0, nother = 0;
@@ -1744,6 +1746,7 @@ int reset_push_status(fwa_engine* e, bool v2bufs = false, const RelTab* tab = nu
 #include "sparse.inc"
 #include "decimal.inc"
 #include "distinct.inc"
+#include "f32fold.inc"
 static const uint64_t kSnapMagic = 0x3150414E53415746ull;   // "FWASNAP1"
 enum { kSnapHdr = 32 };                                       // header words
 #include "reduce.inc"
@@ -1809,6 +1812,7 @@ void fwa_destroy(fwa_engine* e) {
     sp_destroy(e);
     dec_free(e->dec);
     dist_free(e->dist);
+    fold_free(e->fold);
     for (int c = 0; c < 3 + FWA_MAX_AGGS; ++c) if (e->lr_col[c]) (void)hipFree(e->lr_col[c]);
     if (e->d_late) (void)hipFree(e->d_late);
     if (e->d_lr_n) (void)hipFree(e->d_lr_n);
@@ -1847,6 +1851,15 @@ int fwa_create(const fwa_config* ucfg, fwa_engine** out) {
     memset(&uc, 0, sizeof(uc));
     memcpy(&uc, ucfg, ucfg->abi_version == 3 ? offsetof(fwa_config, dec_scale) : sizeof(fwa_config));
     g_create_err.clear();
+    // FWA_CFG_F32_FOLD: the float32 arrival-order fold beside the handle's own SUM_F32 (f32fold.inc); the internal
+    // configuration is not touched, and without a SUM_F32 aggregate the flag does nothing
+    FoldPlan* F = nullptr;
+    if (uc.flags & FWA_CFG_F32_FOLD) {
+        F = new FoldPlan();
+        const int rf = fold_plan(&uc, F, &g_create_err);
+        if (rf || !F->nc) { delete F; F = nullptr; }
+        if (rf) return rf;
+    }
     // COUNT / SUM / AVG(DISTINCT) -> sums of engine-written columns (distinct.inc), before the DECIMAL plan so the two
     // compose; the FWA_AGG_DISTINCT bit is gone from the kinds after the rewrite, so validate never sees it
     DistinctPlan* D = nullptr;
@@ -1854,7 +1867,7 @@ int fwa_create(const fwa_config* ucfg, fwa_engine** out) {
         D = new DistinctPlan();
         fwa_config ic;
         const int rd = dist_plan(&uc, D, &ic, &g_create_err);
-        if (rd) { delete D; return rd; }
+        if (rd) { delete D; delete F; return rd; }
         uc = ic;
     }
     int rc = validate(&uc);
@@ -1870,9 +1883,10 @@ int fwa_create(const fwa_config* ucfg, fwa_engine** out) {
         if (!rc) rc = validate(&ic);
         if (!rc) rc = create_engine(&ic, out);
     }
-    if (rc) { delete P; delete D; return rc; }
+    if (rc) { delete P; delete D; delete F; return rc; }
     (*out)->dec = P;
     (*out)->dist = D;
+    (*out)->fold = F;
     return FWA_OK;
 }
 
@@ -2757,7 +2771,7 @@ int fwa_push_nullable(fwa_engine* e, const int64_t* keys, const int64_t* ts, con
                       const uint8_t* const* null_cols, const int32_t* key_hash, int64_t n, int32_t flags,
                       int64_t* late_dropped_out) {
     if (!e) return FWA_E_STATE;
-    if ((!e->dec && !e->dist) || n <= 0 || n > INT32_MAX || !keys || !ts)
+    if ((!e->dec && !e->dist && !e->fold) || n <= 0 || n > INT32_MAX || !keys || !ts)
         return push_body(e, keys, ts, val_cols, null_cols, key_hash, n, flags, late_dropped_out);
     // COUNT(DISTINCT) columns -> marked columns, DECIMAL columns -> piece columns, on the GPU; then the ordinary push
     // over the internal configuration
@@ -2769,6 +2783,14 @@ int fwa_push_nullable(fwa_engine* e, const int64_t* keys, const int64_t* ts, con
     const uint8_t* dnulls[FWA_MAX_COLS];
     if (e->dist) {   // (host inputs are staged by the marking pass: a device push from here on)
         if (int rc2 = dist_mark(e, &keys, &ts, val_cols, null_cols, n, device, dvals, dnulls)) return rc2;
+        val_cols = dvals;
+        null_cols = dnulls;
+        key_hash = nullptr;
+        device = true;
+        flags |= FWA_PUSH_DEVICE_PTRS;
+    }
+    if (e->fold) {   // the float32 fold of the batch, once, ahead of the ingest and its replays (f32fold.inc)
+        if (int rc3 = fold_pass(e, &keys, &ts, val_cols, null_cols, n, device, dvals, dnulls)) return rc3;
         val_cols = dvals;
         null_cols = dnulls;
         key_hash = nullptr;
@@ -2788,6 +2810,7 @@ int fwa_push_nullable(fwa_engine* e, const int64_t* keys, const int64_t* ts, con
     }
     for (int c = 0; c < FWA_MAX_COLS; ++c) e->dev_override[c] = nullptr;
     dist_collect_timing(e);
+    fold_collect_timing(e);
     return rc;
 }
 
@@ -2899,6 +2922,7 @@ int fwa_push_partials(fwa_engine* e, const int64_t* keys, const int64_t* slice_t
     if (!e) return FWA_E_STATE;
     if (e->dec && !e->restoring) return fail(e, FWA_E_UNSUPPORTED, "partial accumulators of DECIMAL aggregates");
     if (e->dist && !e->restoring) return fail(e, FWA_E_UNSUPPORTED, kDistNoPartials);
+    if (e->fold && !e->restoring) return fail(e, FWA_E_UNSUPPORTED, kFoldNoPartials);
     if (e->red) return fail(e, FWA_E_UNSUPPORTED, "partial accumulators of a DataStream reduction");
     if (e->kind == FWA_SESSION) return fail(e, FWA_E_UNSUPPORTED, "partial accumulators need a slicing window");
     if (n < 0 || (n > 0 && (!keys || !slice_ts || !count))) return fail(e, FWA_E_ARG, "null input column");
@@ -3051,6 +3075,7 @@ int fwa_drain_route(fwa_engine* e, int64_t wm, int32_t parallelism, fwa_routed* 
     memset(out, 0, sizeof(*out));
     if (parallelism < 1 || parallelism > FWA_MAX_DEST) return fail(e, FWA_E_ARG, "fwa_drain_route: parallelism");
     if (e->dist) return fail(e, FWA_E_UNSUPPORTED, kDistNoPartials);
+    if (e->fold) return fail(e, FWA_E_UNSUPPORTED, kFoldNoPartials);
     if (e->red || e->dec || e->kind == FWA_SESSION || e->sparse || !e->cfg.output_on_device ||
         e->cfg.key_kind == FWA_KEY_PREHASHED)
         return fail(e, FWA_E_UNSUPPORTED, "fwa_drain_route: a dense slicing-window handle with output_on_device");
@@ -3155,6 +3180,7 @@ int fwa_fire_partials(fwa_engine* e, const int64_t* rows, int64_t n, int32_t m, 
     if (out) memset(out, 0, sizeof(*out));
     if (late_dropped_out) *late_dropped_out = 0;
     if (e->dist) return fail(e, FWA_E_UNSUPPORTED, kDistNoPartials);
+    if (e->fold) return fail(e, FWA_E_UNSUPPORTED, kFoldNoPartials);
     const int na = e->ec.naggs;
     if (n < 0 || m < 3 || m > 3 + kMaxAggsInt || (n > 0 && !rows) || !acc_cell)
         return fail(e, FWA_E_ARG, "fwa_fire_partials: rows / cells");
@@ -3318,6 +3344,7 @@ int fwa_drain_partials(fwa_engine* e, int64_t wm, fwa_partials* out) {
     if (e->red) return fail(e, FWA_E_UNSUPPORTED, "partial accumulators of a DataStream reduction");
     if (e->dec) return fail(e, FWA_E_UNSUPPORTED, "partial accumulators of DECIMAL aggregates");
     if (e->dist) return fail(e, FWA_E_UNSUPPORTED, kDistNoPartials);
+    if (e->fold) return fail(e, FWA_E_UNSUPPORTED, kFoldNoPartials);
     if (e->kind == FWA_SESSION) return fail(e, FWA_E_UNSUPPORTED, "partial accumulators need a slicing window");
     HIPCHK(e, hipSetDevice(e->cfg.device));
     if (int rc0 = settle_pending(e)) return rc0;
@@ -3396,7 +3423,8 @@ int fwa_drain_partials(fwa_engine* e, int64_t wm, fwa_partials* out) {
 // 21 entries, 22 kg_start, 23 kg_end of the snapshotting handle, 24 nullable_cols, 25 hidden non-NULL
 // counters (columns after the acc_j columns), 26 aggregate input columns (4 bits each), 27 the bitmask of the
 // caller's COUNT(DISTINCT) aggregates, 28 the entries of their set's section behind the body (both 0 for other
-// handles, distinct.inc), 29..31 reserved (0)
+// handles, distinct.inc), 29 the bitmask of the caller's SUM_F32 aggregates folded under FWA_CFG_F32_FOLD, 30 the entries
+// of their section behind everything else (both 0 for other handles, f32fold.inc), 31 reserved (0)
 
 static void snap_header(const fwa_engine* e, int64_t* h, int64_t n) {
     memset(h, 0, sizeof(int64_t) * kSnapHdr);
@@ -3421,6 +3449,7 @@ static void snap_header(const fwa_engine* e, int64_t* h, int64_t n) {
     h[25] = e->ec.naggs - e->ec.nout;
     for (int j = 0; j < e->cfg.num_aggs; ++j) h[26] |= (int64_t)(e->cfg.aggs[j].col & 15) << (4 * j);
     h[27] = e->dist ? e->dist->mask : 0;   // the caller's distinct aggregates (COUNT_DISTINCT, FWA_AGG_DISTINCT); h[28]: their set's entries
+    h[29] = e->fold ? e->fold->mask : 0;   // the caller's folded SUM_F32 aggregates (FWA_CFG_F32_FOLD); h[30]: their section's entries
 }
 
 #include "sessions_host.inc"          // session push, fire, snapshot and restore (they use snap_header)
@@ -3502,12 +3531,17 @@ int fwa_snapshot(fwa_engine* e, fwa_blob* out) {
     std::vector<int64_t> dsec;                         // COUNT(DISTINCT): the set's live entries behind the body
     int64_t dm = 0;
     if (e->dist) { if (int rc = dist_snapshot_section(e, &dsec, &dm)) return rc; }
-    const size_t words0 = kSnapHdr + (size_t)maxp + 1 + (size_t)n * ncb, words = words0 + dsec.size();
+    std::vector<int64_t> fsec;                         // FWA_CFG_F32_FOLD: the fold's live entries, last
+    int64_t fm = 0;
+    if (e->fold) { if (int rc = fold_snapshot_section(e, &fsec, &fm)) return rc; }
+    const size_t words0 = kSnapHdr + (size_t)maxp + 1 + (size_t)n * ncb, words = words0 + dsec.size() + fsec.size();
     int64_t* b = (int64_t*)malloc(words * 8);
     if (!b) return fail(e, FWA_E_OOM, "snapshot blob allocation failed");
     snap_header(e, b, n);
     b[28] = dm;
+    b[30] = fm;
     if (!dsec.empty()) memcpy(b + words0, dsec.data(), 8 * dsec.size());
+    if (!fsec.empty()) memcpy(b + words0 + dsec.size(), fsec.data(), 8 * fsec.size());
     memcpy(b + kSnapHdr, off.data(), 8 * ((size_t)maxp + 1));
     int64_t* body = b + kSnapHdr + maxp + 1;
     std::vector<int64_t> cur(off.begin(), off.end() - 1);
@@ -3551,11 +3585,20 @@ int fwa_restore(fwa_engine* e, const void* const* blobs, const int64_t* sizes, i
         for (int w = 24; w < 27; ++w)
             if (h[w] != ref[w]) return fail(e, FWA_E_ARG, "snapshot nullable-column configuration differs");
         if (h[27] != ref[27]) return fail(e, FWA_E_ARG, "snapshot COUNT(DISTINCT) aggregates differ");
-        const int64_t n = h[21], dm = h[28];
+        if (h[29] != ref[29])
+            return fail(e, FWA_E_ARG, "snapshot FWA_CFG_F32_FOLD aggregates differ (header word 29: the SUM_F32 aggregates "
+                                      "folded in float32 by the snapshotting handle, 0 without the flag)");
+        const int64_t n = h[21], dm = h[28], fm = h[30];
         const size_t dwords = e->dist ? (size_t)maxp + 1 + 4 * (size_t)std::max<int64_t>(dm, 0) : 0;
-        if (n < 0 || dm < 0 || (!e->dist && dm) ||
-            sizes[b] != (int64_t)(8 * (kSnapHdr + maxp + 1 + (size_t)n * ncols + dwords)))
+        const size_t fwords = e->fold ? (size_t)maxp + 1 + 4 * (size_t)std::max<int64_t>(fm, 0) : 0;
+        if (n < 0 || dm < 0 || (!e->dist && dm) || fm < 0 || (!e->fold && fm) ||
+            sizes[b] != (int64_t)(8 * (kSnapHdr + maxp + 1 + (size_t)n * ncols + dwords + fwords)))
             return fail(e, FWA_E_ARG, "snapshot size does not match its entry count");
+    }
+    for (int32_t b = 0; e->fold && b < n_blobs; ++b) {   // FWA_CFG_F32_FOLD: the accumulators of this handle's key groups
+        const int64_t* h = (const int64_t*)blobs[b];
+        const size_t dwords = e->dist ? (size_t)maxp + 1 + 4 * (size_t)h[28] : 0;
+        if (int rc = fold_restore_section(e, h + kSnapHdr + maxp + 1 + (size_t)h[21] * ncols + dwords, h[30])) return rc;
     }
     if (e->kind == FWA_SESSION) return restore_sessions(e, blobs, n_blobs);
     if (e->red) return red_restore(e, blobs, n_blobs);
@@ -3809,6 +3852,10 @@ static int fill_out(fwa_engine* e, int64_t nrows, fwa_out* out) {
         for (int j = 0; j < na; ++j)
             if (e->dist->fkind[j]) { col[j] = e->dist->d_fout[j]; nul[j] = e->dist->d_fnull[j]; width[j] = 8; }
     }
+    if (e->fold) {   // FWA_CFG_F32_FOLD: the folded floats the watermark call left in plan-owned columns (f32fold.inc)
+        for (int j = 0; j < na; ++j)
+            if (e->fold->col_of[j] >= 0 && e->fold->d_out[j]) { col[j] = e->fold->d_out[j]; width[j] = 4; }
+    }
     out->num_aggs = na;
     if (e->cfg.output_on_device) {
         out->on_device = 1;
@@ -3939,6 +3986,8 @@ int fwa_advance_watermark(fwa_engine* e, int64_t wm, fwa_out* out) {
         if (rc) return rc;
         e->late_rows = 0;
     }
+    // FWA_CFG_F32_FOLD: the rows' folded sums are read from the set now, before any later push can rebuild it
+    if (e->fold) { if (int rcf2 = fold_rows(e, nrows)) return rcf2; }
     e->rows_out += nrows;
     e->af_rows = nrows;
     if (out) return fill_out(e, nrows, out);
@@ -3954,7 +4003,8 @@ int fwa_advance_watermark_async(fwa_engine* e, int64_t wm) {
     HIPCHK(e, hipSetDevice(e->cfg.device));
     if (int rcf = finish_afire(e)) return rcf;
     e->af_pend = false;
-    if (e->pend && e->pend_v2 && e->kind == FWA_TUMBLE && wm > e->wm && e->late_rows == 0 && !e->sparse) {
+    // (a handle with FWA_CFG_F32_FOLD completes the fire inside the call: its lookup reads the set behind the fire)
+    if (e->pend && e->pend_v2 && e->kind == FWA_TUMBLE && wm > e->wm && e->late_rows == 0 && !e->sparse && !e->fold) {
         std::vector<FireWindow> hw;
         std::vector<int32_t> hs;
         for (auto& kv : e->live) {   // as speculative_fire: untouched slots emit nothing
@@ -4037,6 +4087,7 @@ int fwa_get_stats(fwa_engine* e, fwa_stats* s) {
     s->live_slices = e->kind == FWA_SESSION ? e->n_ss : e->sparse ? sp_live_windows(e) : (int64_t)e->live.size();
     s->current_watermark = e->wm;
     dist_collect_timing(e);                  // (a COUNT(DISTINCT) marking pass not yet added to ingest_ms)
+    fold_collect_timing(e);                  // (nor an FWA_CFG_F32_FOLD pass)
     s->ingest_launches = e->ingest_launches;
     s->ingest_ms = e->ingest_ms;
     s->ingest_records = e->ingest_records;
@@ -4064,6 +4115,7 @@ int fwa_reset_timers(fwa_engine* e) {
     if (int rc0 = settle_pending(e)) return rc0;
     e->ingest_launches = e->ingest_records = e->replay_records = e->fire_launches = e->fire_rows = 0;
     dist_collect_timing(e);
+    fold_collect_timing(e);
     e->ingest_ms = e->fire_ms = e->partition_ms = e->combine_ms = 0;
     return FWA_OK;
 }
@@ -4092,6 +4144,15 @@ int fwa_set_option(fwa_engine* e, int32_t option, int64_t value) {
                 return fail(e, FWA_E_ARG, "FWA_OPT_DISTINCT_SLOTS: a power of two >= 64");
             e->dist->first_slots = value;
             return FWA_OK;
+        case FWA_OPT_F32_FOLD_SLOTS:
+            if (!e->fold) return fail(e, FWA_E_UNSUPPORTED, "FWA_OPT_F32_FOLD_SLOTS: no SUM_F32 aggregate under FWA_CFG_F32_FOLD");
+            if (e->fold->d_tab) return fail(e, FWA_E_STATE, "FWA_OPT_F32_FOLD_SLOTS: before the first push");
+            if (value < 64 || (value & (value - 1)) || value > ((int64_t)1 << 31))
+                return fail(e, FWA_E_ARG, "FWA_OPT_F32_FOLD_SLOTS: a power of two >= 64");
+            e->fold->first_slots = value;
+            return FWA_OK;
+        case FWA_OPT_F32_FOLD_REBUILDS: case FWA_OPT_F32_FOLD_RESOLVE_US: case FWA_OPT_F32_FOLD_SORT_US:
+        case FWA_OPT_F32_FOLD_RUNS_US: case FWA_OPT_F32_FOLD_ROWS_US:
         case FWA_OPT_DISTINCT_LIVE: case FWA_OPT_DISTINCT_REBUILDS: case FWA_OPT_STRAGGLERS: case FWA_OPT_KEY_TABLE_DIGEST:
         case FWA_OPT_DISTINCT_INDEX_US: case FWA_OPT_DISTINCT_COUNT_US: case FWA_OPT_DISTINCT_COUNT_STEPS:
             return fail(e, FWA_E_ARG, "read-only option");
@@ -4138,6 +4199,15 @@ int fwa_get_option(const fwa_engine* e, int32_t option, int64_t* value) {
             if (!e->dist) return FWA_E_UNSUPPORTED;
             *value = option == FWA_OPT_DISTINCT_SLOTS ? (e->dist->slots ? e->dist->slots : e->dist->first_slots)
                    : option == FWA_OPT_DISTINCT_LIVE ? e->dist->live : e->dist->rebuilds;
+            return FWA_OK;
+        case FWA_OPT_F32_FOLD_SLOTS: case FWA_OPT_F32_FOLD_REBUILDS: case FWA_OPT_F32_FOLD_RESOLVE_US:
+        case FWA_OPT_F32_FOLD_SORT_US: case FWA_OPT_F32_FOLD_RUNS_US: case FWA_OPT_F32_FOLD_ROWS_US:
+            if (!e->fold) return FWA_E_UNSUPPORTED;
+            *value = option == FWA_OPT_F32_FOLD_SLOTS ? (e->fold->slots ? e->fold->slots : e->fold->first_slots)
+                   : option == FWA_OPT_F32_FOLD_REBUILDS ? e->fold->rebuilds
+                   : (int64_t)(1000.0 * (option == FWA_OPT_F32_FOLD_RESOLVE_US ? e->fold->resolve_ms
+                                         : option == FWA_OPT_F32_FOLD_SORT_US ? e->fold->sort_ms
+                                         : option == FWA_OPT_F32_FOLD_RUNS_US ? e->fold->fold_ms : e->fold->rows_ms));
             return FWA_OK;
         case FWA_OPT_DISTINCT_INDEX_US: case FWA_OPT_DISTINCT_COUNT_US: case FWA_OPT_DISTINCT_COUNT_STEPS:
             if (!e->dist || !e->dist->range) return FWA_E_UNSUPPORTED;

@@ -278,9 +278,16 @@ struct In {
 
 // Layouts this file writes: DataStream TUMBLE and SESSION (WindowOperator), Table TUMBLE / HOP / CUMULATE
 // (SlicingWindowOperator: per-slice state, so the engine's slices map 1:1), Table shift time zones and SQL NULLs.
+// FWA_CFG_F32_FOLD with a SUM_F32 aggregate: the float32 fold lives beside the accumulators this file writes
+bool folds_f32(const fwa_config& c) {
+    if (!(c.flags & FWA_CFG_F32_FOLD)) return false;
+    for (int j = 0; j < c.num_aggs; ++j) if (c.aggs[j].kind == FWA_SUM_F32) return true;
+    return false;
+}
 bool supported(const fwa_config& c, bool dict = false) {
     if (c.key_kind == FWA_KEY_PREHASHED) return false;
     if (c.flags & FWA_CFG_REDUCE) return false;                        // a reduction keeps the reduced element
+    if (folds_f32(c)) return false;                                    // the Float sum buffer is not written
     for (int j = 0; j < c.num_aggs; ++j)                               // reduce kinds: the reduced element, no ACC
         if (c.aggs[j].kind >= FWA_SUM_I32) return false;
     if ((c.key_kind == FWA_KEY_GROUP_PREFIXED) != dict) return false;   // dictionary ids <=> a key dictionary
@@ -295,7 +302,10 @@ const char* kUnsupported = "heap layout: DataStream TUMBLE / SLIDE / SESSION agg
 // COUNT(DISTINCT) handles have their own reason: the reference keeps the distinct values as MapView bytes
 const char* kNoDistinct = "heap layout of COUNT(DISTINCT): the set of values (MapView bytes in the reference) is not "
                           "written; fwa_snapshot / fwa_restore carry it";
+const char* kNoFold = "heap layout under FWA_CFG_F32_FOLD: the Float sum buffer of the arrival-order fold is not "
+                      "written; fwa_snapshot / fwa_restore carry it";
 const char* why_unsupported(const fwa_config& c) {
+    if (folds_f32(c)) return kNoFold;
     for (int j = 0; j < c.num_aggs; ++j)                               // (FWA_AGG_DISTINCT: SUM / AVG(DISTINCT), same view)
         if (c.aggs[j].kind == FWA_COUNT_DISTINCT || (c.aggs[j].kind & FWA_AGG_DISTINCT)) return kNoDistinct;
     return kUnsupported;

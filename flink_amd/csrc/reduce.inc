@@ -25,8 +25,10 @@
 // under atomicMax (ties to the last), exactly the arrival-order fold. The fire (red_fire_kernel) merges the slices of
 // a window (SLIDE: slices of gcd(size, slide)): sums add, MIN / MAX fold, and the selection is the slice whose
 // (by-value, seq) is best -- the element the window's own ReducingState would hold. Records that fire a window already
-// past its trigger (allowed lateness > 0) are applied one by one in arrival order by red_late_fire_kernel. Non-merging
-// windows only (validate()); integer sums wrap like Java, a Float SUM is summed in double and rounded once.
+// past its trigger (allowed lateness > 0) are applied one by one in arrival order by red_late_fire_kernel. TUMBLE and
+// SLIDE windows, and session windows of a Tuple2<key, field> (validate()); integer sums wrap like Java, a Float SUM is
+// summed in double and rounded once unless the handle asks for the float32 arrival-order fold (FWA_CFG_F32_FOLD,
+// f32fold.inc).
 
 namespace {
 

@@ -49,7 +49,13 @@ def _col_dtypes(aggs, ncols):
 
 
 class _Base:
-    def __init__(self, spec: WindowSpec, aggs, batch_size=1 << 20, engine_factory=None, track_late=False, **cfg_kw):
+    def __init__(self, spec: WindowSpec, aggs, batch_size=1 << 20, engine_factory=None, track_late=False,
+                 f32_fold=False, **cfg_kw):
+        """f32_fold (WindowOperator, ReduceWindowOperator and SlicingWindowProcessor alike): every SUM_F32 is the
+        reference's float32 arrival-order fold, bit for bit (FWA_CFG_F32_FOLD: TUMBLE windows, no allowed lateness).
+        Set it for DataStream float sums and ONE_PHASE Table plans, not for the two-phase plan."""
+        if f32_fold:
+            cfg_kw["f32_fold"] = True
         if engine_factory is None:
             from .engine import WindowAggregator
             engine_factory = WindowAggregator

@@ -22,8 +22,10 @@ def parse(blob):
     prehashed = int(w[10]) == 2                  # FWA_KEY_PREHASHED: a last column holds each key's key.hashCode()
     ncols = (4 if session else 3) + naggs + nh + (1 if prehashed else 0)   # nh: hidden non-NULL counters
     dmask, dm = int(w[27]), int(w[28])           # COUNT(DISTINCT): aggregate bitmask, entries of the distinct set
+    fmask, fm = int(w[29]), int(w[30])           # FWA_CFG_F32_FOLD: folded SUM_F32 bitmask, entries of the fold's section
     body_end = HDR_WORDS + maxp + 1 + n * ncols
-    need = body_end + (maxp + 1 + 4 * dm if dmask else 0)
+    dist_end = body_end + (maxp + 1 + 4 * dm if dmask else 0)
+    need = dist_end + (maxp + 1 + 4 * fm if fmask else 0)
     if w.size != need:
         raise ValueError("snapshot size %d words != %d" % (w.size, need))
     off = w[HDR_WORDS:HDR_WORDS + maxp + 1]
@@ -42,10 +44,15 @@ def parse(blob):
     if prehashed:
         out["key_hash"] = body[ncols - 1].astype(np.int32)
     if dmask:                                    # the live (key, value, slice, column) entries behind the body
-        sec = w[body_end + maxp + 1:].reshape(4, dm) if dm else np.zeros((4, 0), np.int64)
+        sec = w[body_end + maxp + 1:dist_end].reshape(4, dm) if dm else np.zeros((4, 0), np.int64)
         out["distinct"] = {"agg_mask": dmask, "n": dm, "kg_offsets": w[body_end:body_end + maxp + 1].copy(),
                            "key": sec[0].copy(), "value": sec[1].copy(), "slice_start": sec[2].copy(),
                            "column": sec[3].copy()}
+    if fmask:                                    # the live float32 accumulators, last: (key, slice, column, bits)
+        sec = w[dist_end + maxp + 1:].reshape(4, fm) if fm else np.zeros((4, 0), np.int64)
+        out["f32_fold"] = {"agg_mask": fmask, "n": fm, "kg_offsets": w[dist_end:dist_end + maxp + 1].copy(),
+                           "key": sec[0].copy(), "slice_start": sec[1].copy(), "column": sec[2].copy(),
+                           "acc": sec[3].astype(np.uint32).view(np.float32)}
     return out
 
 

@@ -344,6 +344,43 @@ typedef struct fwa_config {
                                        * fwa_restore carry the set: one section entry per set bit, its slice start the
                                        * cell's start (cell * gap_ms, local time). No effect on a handle that is not
                                        * SESSION; without it a SESSION handle refuses the distinct aggregates. */
+#define FWA_CFG_F32_FOLD 0x80 /* SUM(FLOAT) exactly as the reference computes it. Without the flag FWA_SUM_F32 adds in
+                               * double and rounds once (deterministic, within ~1e-7 relative of the reference, not its
+                               * bits). With it every FWA_SUM_F32 aggregate of the handle returns, per fired
+                               * (key, window): acc = +0.0f; for each accepted non-NULL record of that (key, window) in
+                               * arrival order (batch position within a push, pushes in call order)
+                               * acc = (float)(acc + v); the result is acc -- SumAggFunction's FLOAT buffer
+                               * (SumAggFunction.java:133-139) and SumAggregator.reduce on a Float field
+                               * (SumAggregator.java:66-76), bit for bit. FWA_AVG_F32 / MIN_F32 / MAX_F32 are untouched
+                               * (the reference's float AVG sums in double already).
+                               * Start value: the fold starts from +0.0f, so a window holding only -0.0 gives +0.0 where
+                               * the reference keeps -0.0: the one difference that remains. Special values: NaN, or +Inf
+                               * together with -Inf, give NaN (returned canonical on FWA_CFG_REDUCE handles, as without
+                               * the flag). NULL inputs are skipped; the NULL flag of a Table result comes from the
+                               * hidden non-NULL counter, unchanged. Records the ingest drops as late do not enter the
+                               * fold; late_dropped, fwa_late_records and every other column are unaffected.
+                               * Accepted: FWA_TUMBLE with Table semantics (a shift time zone, nullable columns,
+                               * FWA_CFG_LATE_INDICES, the dense and the record-list layouts) or with DataStream semantics
+                               * and allowed_lateness_ms == 0 (plain aggregates and FWA_CFG_REDUCE: sum(pos) on a Float
+                               * field, other FWA_SUM_F32 fields of the tuple are folded too); key kinds JAVA_LONG,
+                               * BINROW_BIGINT, GROUP_PREFIXED; several FWA_SUM_F32 aggregates (those over one column
+                               * share their fold); DECIMAL aggregates may share the handle. Refused at fwa_create with
+                               * FWA_E_UNSUPPORTED (fwa_last_error names the flag): DataStream SLIDE (a window's
+                               * arrival-order fold is not a function of per-slice folds), HOP / CUMULATE / SESSION,
+                               * allowed_lateness_ms > 0, FWA_KEY_PREHASHED, a handle that also has DISTINCT aggregates,
+                               * windows shorter than 4 ms; on an accepted handle fwa_drain_partials, fwa_push_partials,
+                               * fwa_drain_route, fwa_fire_partials (a fold split across ranks is the two-phase plan,
+                               * which has no single float32 result) and fwa_snapshot_heap* / fwa_restore_heap*. On a
+                               * handle with no FWA_SUM_F32 aggregate the flag is accepted and does nothing.
+                               * Cost: one pass per push ahead of the ingest (resolve, a stable sort, the serial fold of
+                               * each (key, window)'s records: FWA_OPT_F32_FOLD_*_US, part of fwa_stats.ingest_ms) and a
+                               * lookup per fired row; the handle completes its fire inside
+                               * fwa_advance_watermark_async. fwa_snapshot appends the live accumulators as a last
+                               * section (header words 29 and 30) and fwa_restore continues every fold where the
+                               * snapshot left it, rescaled or not; blobs of handles without the flag keep their bytes.
+                               * Failure rule, as for DISTINCT handles: a push that fails behind the fold pass (a
+                               * foreign key group, FWA_E_TS_MIN, a device error) has already folded its values -- the
+                               * handle is to be restored from its last snapshot, not retried. */
 
 typedef struct fwa_out {
     int64_t n_rows;
@@ -366,7 +403,8 @@ typedef struct fwa_stats {
     int64_t current_watermark;
     /* device time of the engine's kernels, measured with HIP events on the handle's stream */
     int64_t ingest_launches;
-    double ingest_ms;            /* sum over ingest-kernel launches, and over the marking passes of COUNT(DISTINCT) handles */
+    double ingest_ms;            /* sum over ingest-kernel launches, and over the marking passes of COUNT(DISTINCT) handles
+                                    and the fold passes of FWA_CFG_F32_FOLD handles */
     int64_t ingest_records;      /* distinct records pushed through those launches (replays excluded) */
     int64_t fire_launches;
     double fire_ms;
@@ -662,8 +700,17 @@ enum fwa_option {
     FWA_OPT_DISTINCT_COUNT_US = 24, /* read only, the same handles: ... and scanning the set for the counts (session
                                        mode: the clear of the fired sessions' bits included) */
     FWA_OPT_DISTINCT_COUNT_STEPS = 25, /* read only, the same handles: firing steps counted so far */
-    FWA_OPT_STALE_RETIRES = 26   /* read only: slots the tumbling fire retired without storing their identities, left
+    FWA_OPT_STALE_RETIRES = 26,  /* read only: slots the tumbling fire retired without storing their identities, left
                                     for the next two-phase push to overwrite (fwa_get_option) */
+    FWA_OPT_F32_FOLD_SLOTS = 27, /* FWA_CFG_F32_FOLD: first size of the fold's set in slots (a power of two >= 64, before
+                                    the first push; tests force growth); fwa_get_option: the current size. Handles
+                                    without a folded aggregate: FWA_E_UNSUPPORTED */
+    FWA_OPT_F32_FOLD_REBUILDS = 28,   /* read only: rebuilds of that set (growth, dropping fired windows' entries) */
+    FWA_OPT_F32_FOLD_RESOLVE_US = 29, /* read only: device microseconds the fold passes so far spent resolving records
+                                         to entries, */
+    FWA_OPT_F32_FOLD_SORT_US = 30,    /* ... sorting (entry, record index), */
+    FWA_OPT_F32_FOLD_RUNS_US = 31,    /* ... and folding the runs (all three are part of fwa_stats.ingest_ms) */
+    FWA_OPT_F32_FOLD_ROWS_US = 32     /* read only: ... and the fires' lookups of the rows' sums (part of fire_ms) */
 };
 int fwa_set_option(fwa_engine* e, int32_t option, int64_t value);
 /* The option's effective value: for the tri-state options 1 if the handle currently takes that path (forced, or
