@@ -1071,6 +1071,7 @@ struct fwa_engine {
     int32_t n_stale = 0;
     std::vector<std::pair<int64_t, int32_t>> push_stale;   // (slice, slot): stale slots the pending push may overwrite
     int64_t stale_retires = 0;          // slots retired stale (FWA_OPT_STALE_RETIRES)
+    int64_t fast_slice_pushes = 0;      // two-phase pushes whose Phase P had the 32-bit slice division armed (FWA_OPT_FAST_SLICE_PUSHES)
     bool steady = false;                // the last settled push ran the two-phase ingest and needed no replay
     // slice directory
     DirEntry* d_dir = nullptr;
@@ -4155,6 +4156,7 @@ int fwa_set_option(fwa_engine* e, int32_t option, int64_t value) {
         case FWA_OPT_F32_FOLD_RUNS_US: case FWA_OPT_F32_FOLD_ROWS_US:
         case FWA_OPT_DISTINCT_LIVE: case FWA_OPT_DISTINCT_REBUILDS: case FWA_OPT_STRAGGLERS: case FWA_OPT_KEY_TABLE_DIGEST:
         case FWA_OPT_DISTINCT_INDEX_US: case FWA_OPT_DISTINCT_COUNT_US: case FWA_OPT_DISTINCT_COUNT_STEPS:
+        case FWA_OPT_FAST_SLICE_PUSHES:
             return fail(e, FWA_E_ARG, "read-only option");
         default: return fail(e, FWA_E_ARG, "unknown option");
     }
@@ -4185,6 +4187,7 @@ int fwa_get_option(const fwa_engine* e, int32_t option, int64_t* value) {
         case FWA_OPT_RESET_LAUNCHES: *value = e->reset_launches; return FWA_OK;
         case FWA_OPT_STALE_RETIRES: *value = e->stale_retires; return FWA_OK;
         case FWA_OPT_STRAGGLERS: *value = e->stragglers; return FWA_OK;
+        case FWA_OPT_FAST_SLICE_PUSHES: *value = e->fast_slice_pushes; return FWA_OK;
         case FWA_OPT_KEY_TABLE_DIGEST: {   // FNV-1a over the table's words in slot order (the side slot included)
             std::vector<unsigned long long> table((size_t)e->capacity + 1);
             if (!e->d_keys || hipStreamSynchronize(e->stream) != hipSuccess ||

@@ -163,17 +163,15 @@ static int fill_part_args(fwa_engine* e, const IngestArgs& a, const V2Shape& s, 
     pa.epoch = std::max<int32_t>(1, e->push_epoch);
     pa.spill = e->d_spill;
     pa.q_base = q_base;
-    if (!e->cfg.tz_n && e->g > 0 && (uint64_t)e->g * kRelCap < (1ull << 32) && q_base > -(1ll << 40) && q_base < (1ll << 40)) {
-        // floor(n / g) = (n * ceil(2^(32+L) / g)) >> (32+L) for every n < 2^32, L = ceil(log2 g) (round-up method;
-        // the magic has at most 33 bits, so n * m fits 64 bits)
-        int L = 0;
-        while ((1ull << L) < (uint64_t)e->g) ++L;
+    const jm::FastSlice fs = jm::fast_slice_make(e->g, kRelCap);
+    if (!e->cfg.tz_n && fs.m && q_base > -(1ll << 40) && q_base < (1ll << 40)) {
         const __int128 b = (__int128)e->off + (__int128)q_base * e->g;
         if (b > (__int128)INT64_MIN / 2 && b < (__int128)INT64_MAX / 2) {
-            pa.fast_sh = 32 + L;
-            pa.fast_m = ((1ull << (32 + L)) + (uint64_t)e->g - 1) / (uint64_t)e->g;
-            pa.fast_lim = (uint64_t)e->g * kRelCap;
+            pa.fast_sh = fs.sh;
+            pa.fast_m = fs.m;
+            pa.fast_lim = fs.lim;
             pa.base_ts = (int64_t)b;
+            e->fast_slice_pushes++;
         }
     }
     pa.b_key = e->d_bkey;

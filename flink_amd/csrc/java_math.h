@@ -170,6 +170,26 @@ JM_HD uint64_t udiv64(uint64_t n, const UDiv64& dv) {
     return t >> dv.shift;
 }
 
+// Phase P's 32-bit slice division (ingest.inc, partition3_kernel): floor(n / g) = (n * m) >> sh for every n < lim =
+// g * table (round-up method: m = ceil(2^sh / g), sh = 32 + ceil(log2 g); the magic has at most 33 bits, so n * m fits
+// 64 bits). m == 0: not armed -- g * table reaches 2^32, and the kernel takes the exact 64-bit division.
+struct FastSlice {
+    uint64_t m, lim;
+    int32_t sh;
+};
+static inline FastSlice fast_slice_make(int64_t g, int64_t table) {
+    FastSlice r;
+    r.m = r.lim = 0;
+    r.sh = 0;
+    if (g <= 0 || table <= 0 || (unsigned __int128)g * (unsigned __int128)table >= ((unsigned __int128)1 << 32)) return r;
+    int L = 0;
+    while ((1ull << L) < (uint64_t)g) ++L;
+    r.sh = 32 + L;
+    r.m = ((1ull << (32 + L)) + (uint64_t)g - 1) / (uint64_t)g;
+    r.lim = (uint64_t)g * (uint64_t)table;
+    return r;
+}
+
 // Java long '%' by positive d (sign follows the dividend), with d given as a magic divider.
 JM_HD int64_t jrem(int64_t a, const UDiv64& dv) {
     uint64_t ua = a < 0 ? (uint64_t)0 - (uint64_t)a : (uint64_t)a;

@@ -279,7 +279,9 @@ typedef struct fwa_config {
     int32_t semantics;           /* enum fwa_semantics */
     int32_t key_kind;            /* enum fwa_key_kind */
     int64_t size_ms;             /* TUMBLE size; SLIDE size; CUMULATE max size */
-    int64_t slide_ms;            /* SLIDE slide; CUMULATE step; unused otherwise */
+    int64_t slide_ms;            /* SLIDE slide; CUMULATE step; unused otherwise. Table SLIDE (HOP) and CUMULATE: size_ms
+                                    must be a multiple of slide_ms, as in the reference (SliceAssigners.java:214-220);
+                                    fwa_create answers FWA_E_ARG otherwise. DataStream SLIDE takes any pair. */
     int64_t offset_ms;           /* window offset (assigner 'offset'); 0 = epoch aligned */
     int64_t gap_ms;              /* SESSION gap */
     int64_t allowed_lateness_ms; /* DATASTREAM only (WindowOperator allowedLateness) */
@@ -710,7 +712,11 @@ enum fwa_option {
                                          to entries, */
     FWA_OPT_F32_FOLD_SORT_US = 30,    /* ... sorting (entry, record index), */
     FWA_OPT_F32_FOLD_RUNS_US = 31,    /* ... and folding the runs (all three are part of fwa_stats.ingest_ms) */
-    FWA_OPT_F32_FOLD_ROWS_US = 32     /* read only: ... and the fires' lookups of the rows' sums (part of fire_ms) */
+    FWA_OPT_F32_FOLD_ROWS_US = 32,    /* read only: ... and the fires' lookups of the rows' sums (part of fire_ms) */
+    FWA_OPT_FAST_SLICE_PUSHES = 33    /* read only: two-phase pushes so far whose Phase P turned timestamps into slice
+                                         numbers with its 32-bit division: no shift time zone, slice size * 4096 below
+                                         2^32 ms and the first live slice number inside +-2^40; every other two-phase
+                                         push takes the exact 64-bit floor division (fwa_get_option) */
 };
 int fwa_set_option(fwa_engine* e, int32_t option, int64_t value);
 /* The option's effective value: for the tri-state options 1 if the handle currently takes that path (forced, or
