@@ -102,6 +102,13 @@ CFG_F32_FOLD = 0x80
 PUSH_DEVICE_PTRS = 0x1
 PUSH_ASYNC = 0x2
 
+OPT_KEY_TABLE_SHAPE = 34          # read only (engine.OPTIONS "key_table_shape"): seg_log | part_bits << 8
+
+
+def key_table_shape(value):
+    """(seg_log, part_bits) of an FWA_OPT_KEY_TABLE_SHAPE value: 2^part_bits segments of 2^seg_log slots."""
+    return int(value) & 0xff, int(value) >> 8
+
 LONG_MIN = -(1 << 63)
 LONG_MAX = (1 << 63) - 1
 

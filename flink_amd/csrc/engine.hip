@@ -4156,7 +4156,7 @@ int fwa_set_option(fwa_engine* e, int32_t option, int64_t value) {
         case FWA_OPT_F32_FOLD_RUNS_US: case FWA_OPT_F32_FOLD_ROWS_US:
         case FWA_OPT_DISTINCT_LIVE: case FWA_OPT_DISTINCT_REBUILDS: case FWA_OPT_STRAGGLERS: case FWA_OPT_KEY_TABLE_DIGEST:
         case FWA_OPT_DISTINCT_INDEX_US: case FWA_OPT_DISTINCT_COUNT_US: case FWA_OPT_DISTINCT_COUNT_STEPS:
-        case FWA_OPT_FAST_SLICE_PUSHES:
+        case FWA_OPT_FAST_SLICE_PUSHES: case FWA_OPT_KEY_TABLE_SHAPE:
             return fail(e, FWA_E_ARG, "read-only option");
         default: return fail(e, FWA_E_ARG, "unknown option");
     }
@@ -4188,6 +4188,10 @@ int fwa_get_option(const fwa_engine* e, int32_t option, int64_t* value) {
         case FWA_OPT_STALE_RETIRES: *value = e->stale_retires; return FWA_OK;
         case FWA_OPT_STRAGGLERS: *value = e->stragglers; return FWA_OK;
         case FWA_OPT_FAST_SLICE_PUSHES: *value = e->fast_slice_pushes; return FWA_OK;
+        case FWA_OPT_KEY_TABLE_SHAPE:      // record lists keep no key table
+            if (e->sparse) return FWA_E_UNSUPPORTED;
+            *value = (int64_t)e->seg_log | ((int64_t)e->part_bits << 8);
+            return FWA_OK;
         case FWA_OPT_KEY_TABLE_DIGEST: {   // FNV-1a over the table's words in slot order (the side slot included)
             std::vector<unsigned long long> table((size_t)e->capacity + 1);
             if (!e->d_keys || hipStreamSynchronize(e->stream) != hipSuccess ||

@@ -713,10 +713,15 @@ enum fwa_option {
     FWA_OPT_F32_FOLD_SORT_US = 30,    /* ... sorting (entry, record index), */
     FWA_OPT_F32_FOLD_RUNS_US = 31,    /* ... and folding the runs (all three are part of fwa_stats.ingest_ms) */
     FWA_OPT_F32_FOLD_ROWS_US = 32,    /* read only: ... and the fires' lookups of the rows' sums (part of fire_ms) */
-    FWA_OPT_FAST_SLICE_PUSHES = 33    /* read only: two-phase pushes so far whose Phase P turned timestamps into slice
+    FWA_OPT_FAST_SLICE_PUSHES = 33,   /* read only: two-phase pushes so far whose Phase P turned timestamps into slice
                                          numbers with its 32-bit division: no shift time zone, slice size * 4096 below
                                          2^32 ms and the first live slice number inside +-2^40; every other two-phase
                                          push takes the exact 64-bit floor division (fwa_get_option) */
+    FWA_OPT_KEY_TABLE_SHAPE = 34      /* read only: the key table's segmentation, seg_log | part_bits << 8 -- the table
+                                         is 2^part_bits segments of 2^seg_log slots; mix64(key)'s top part_bits pick the
+                                         segment, its low seg_log bits (rounded down to an 8-slot bucket) the home slot
+                                         inside it (fwa_get_option; diagnostic: tests aim key sets with it). Handles
+                                         that keep record lists have no key table: FWA_E_UNSUPPORTED */
 };
 int fwa_set_option(fwa_engine* e, int32_t option, int64_t value);
 /* The option's effective value: for the tri-state options 1 if the handle currently takes that path (forced, or

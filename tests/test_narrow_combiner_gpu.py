@@ -13,6 +13,7 @@ import pytest
 
 from flink_amd import _abi as A
 from helpers import assert_rows_equal
+from key_place import mix64
 
 pytestmark = pytest.mark.gpu
 
@@ -23,14 +24,6 @@ IT = 6                            # entries per lane and chunk of the narrow com
 TILE = 6 * 1024                   # records per partition3 tile; tile t of a push feeds sub-bucket t % 16
 OLD_BODY = 2                      # FWA_OPT_INGEST_VARIANT bit 1
 I32_MIN, I32_MAX = -2**31, 2**31 - 1
-
-
-def mix64(z):
-    z = np.asarray(z, np.int64).astype(np.uint64)
-    with np.errstate(over="ignore"):
-        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xbf58476d1ce4e5b9)
-        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94d049bb133111eb)
-    return z ^ (z >> np.uint64(31))
 
 
 def seg_of(keys):

@@ -18,6 +18,7 @@ import pytest
 
 from flink_amd import _abi as A
 from helpers import assert_rows_equal
+from key_place import mix64
 
 pytestmark = pytest.mark.gpu
 
@@ -27,14 +28,6 @@ IDENTITY_STORES = 512                            # FWA_OPT_INGEST_VARIANT bit 9
 OLD_BODY = 2                                     # bit 1
 NKEYS = 3000
 I32 = 2**31
-
-
-def mix64(z):
-    z = np.asarray(z, np.int64).astype(np.uint64)
-    with np.errstate(over="ignore"):
-        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xbf58476d1ce4e5b9)
-        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94d049bb133111eb)
-    return z ^ (z >> np.uint64(31))
 
 
 def batch(rng, keys, n, lo_ms, hi_ms, wm, sort=True):
