@@ -103,6 +103,7 @@ PUSH_DEVICE_PTRS = 0x1
 PUSH_ASYNC = 0x2
 
 OPT_KEY_TABLE_SHAPE = 34          # read only (engine.OPTIONS "key_table_shape"): seg_log | part_bits << 8
+OPT_HEAP_KEY_POS = 35             # engine.OPTIONS "heap_key_pos": the key's position in a reduced tuple (-1: not declared)
 
 
 def key_table_shape(value):

@@ -1241,6 +1241,7 @@ struct fwa_engine {
     double mf_capx = 2.0;                 // bucket region = mean rows per bucket x this (+ slack); grows on overflow
     int32_t opt_fire_partials = -1;       // FWA_OPT_FIRE_PARTIALS: -1 / 1 the merge-fire path where eligible, 0 never
     int32_t opt_dec_wrap_null = 0;        // FWA_OPT_DEC_WRAP_NULL: 1 emits NULL for a wrapped DECIMAL window, 0 fails
+    int32_t opt_heap_key_pos = -1;        // FWA_OPT_HEAP_KEY_POS: the key's position in a reduced tuple (-1: not declared)
     int64_t mf_calls = 0, mf_fallbacks = 0;
     // fwa_drain_route: send regions [par][dr_cap][cells] and the per-destination row counters (d_dr_cnt)
     int64_t* d_dr = nullptr;
@@ -4138,6 +4139,11 @@ int fwa_set_option(fwa_engine* e, int32_t option, int64_t value) {
         case FWA_OPT_SLIDE_CARRIED: e->rs_on = value != 0; e->rs_valid = false; return FWA_OK;
         case FWA_OPT_FIRE_PARTIALS: e->opt_fire_partials = value != 0 ? 1 : 0; return FWA_OK;
         case FWA_OPT_DEC_WRAP_NULL: e->opt_dec_wrap_null = value != 0 ? 1 : 0; return FWA_OK;
+        case FWA_OPT_HEAP_KEY_POS:
+            if (value < 0 || value > (e->dist ? e->dist->ucfg.num_aggs : e->dec ? e->dec->ucfg.num_aggs : e->cfg.num_aggs))
+                return fail(e, FWA_E_ARG, "FWA_OPT_HEAP_KEY_POS: the key's tuple position, 0 .. num_aggs");
+            e->opt_heap_key_pos = (int32_t)value;
+            return FWA_OK;
         case FWA_OPT_DISTINCT_SLOTS:
             if (!e->dist) return fail(e, FWA_E_UNSUPPORTED, "FWA_OPT_DISTINCT_SLOTS: no COUNT(DISTINCT) aggregate");
             if (e->dist->d_tab) return fail(e, FWA_E_STATE, "FWA_OPT_DISTINCT_SLOTS: before the first push");
@@ -4183,6 +4189,7 @@ int fwa_get_option(const fwa_engine* e, int32_t option, int64_t* value) {
         case FWA_OPT_SLIDE_CARRIED: *value = e->rs_used; return FWA_OK;
         case FWA_OPT_FIRE_PARTIALS: *value = e->mf_calls - e->mf_fallbacks; return FWA_OK;
         case FWA_OPT_DEC_WRAP_NULL: *value = e->opt_dec_wrap_null; return FWA_OK;
+        case FWA_OPT_HEAP_KEY_POS: *value = e->opt_heap_key_pos; return FWA_OK;
         case FWA_OPT_FUSED_FIRES: *value = e->fused_fires; return FWA_OK;
         case FWA_OPT_RESET_LAUNCHES: *value = e->reset_launches; return FWA_OK;
         case FWA_OPT_STALE_RETIRES: *value = e->stale_retires; return FWA_OK;

@@ -35,8 +35,28 @@
 // DECIMAL SUM / AVG (Table): the accumulator field is the DECIMAL(38, s) running sum (findSumAggType), rebuilt from the
 // engine's 32-bit piece sums (decimal.inc) and written as a non-compact DecimalData; AVG's count is COUNT(*) or the
 // column's hidden non-NULL counter, already in the row.
-// PREHASHED keys (their Java serialization is the caller's) and DataStream reductions: FWA_E_UNSUPPORTED; the engine
-// format (fwa_snapshot, FWASNAP1) carries both, PREHASHED keys with the hash column of their key groups.
+// DataStream reductions (FWA_CFG_REDUCE; WindowedStream.sum / min / max / minBy / maxBy): the window-contents value is
+// the ReducingState's element, the reduced tuple itself (TupleSerializer: the fields in order, big-endian, no null
+// mask) -- the key at the tuple position FWA_OPT_HEAP_KEY_POS declares, the handle's aggregates as the other fields in
+// order, 8 bytes for *_I64 / *_F64 / FIRST_64 / SEL_64 and 4 for *_I32 / *_F32 / FIRST_32 / SEL_32. TUMBLE (any allowed
+// lateness): one entry per FWASNAP1 (key, window) entry, its cells as they stand (a 4-byte field is the cell's low 32
+// bits), the hidden selection columns left out; SESSION over Tuple2<key, f1>: the session layout above with that value.
+// State ids and timers as for aggregates. A restore turns each state entry into one FWASNAP1 reduce entry whose count
+// column (the arrival rank that orders red_restore) is the entry's running index: a ReducingState holds one element
+// and every later element folds after it, so first-element and tie rules continue as in the reference.
+// String keys (DataStream handles with FWA_KEY_PREHASHED on the ids of a one-field STRING key dictionary whose values
+// are the canonical char bytes of a java.lang.String, fwa_snapshot_heap_keys / fwa_restore_heap_keys): a key is
+// written as StringSerializer writes it (StringValue.writeString: varint(len + 1), len = UTF-16 code units = stored
+// bytes with bit 7 clear, then the stored char bytes); an entry's key group is the one its FWASNAP1 hash column gives
+// (never bits 48-63 of the id: those are the BinaryRowData hash's group). A restore parses each key (the null string,
+// a non-canonical char coding or an overrun is a malformed body), encodes the distinct ones into the target
+// dictionary and feeds String.hashCode() over the code units (fwa_jstring_hash's value) to the hash column.
+// FWA_E_UNSUPPORTED, each with its reason in fwa_last_error: SLIDE reductions (the reference keeps one reduced element
+// per window, the engine one per slice, and without the arrival ranks a window's first or selected element cannot be
+// placed in a slice); FWA_CFG_F32_FOLD handles; a reduce handle without FWA_OPT_HEAP_KEY_POS; PREHASHED keys without a
+// dictionary, or under Table semantics (their Java serialization is the caller's); a dictionary under DataStream
+// semantics that is not exactly one STRING field, or beside a JAVA_LONG handle; DISTINCT sets. Other Java key types
+// stay on the engine format (fwa_snapshot, FWASNAP1: PREHASHED keys with the hash column of their key groups).
 #include <algorithm>
 #include <cstdint>
 #include <map>
@@ -71,7 +91,8 @@ bool parse(const void* p, int64_t bytes, Snap* s) {
     s->nh = w[25];
     if (s->naggs < 0 || s->naggs > FWA_MAX_AGGS || s->maxp <= 0 || s->nh < 0 || s->nh > FWA_MAX_COLS) return false;
     for (int j = 0; j < s->naggs; ++j) s->agg[j] = w[12 + j];
-    const int64_t ncols = (s->kind == FWA_SESSION ? 4 : 3) + s->naggs + s->nh;
+    // (PREHASHED handles: one more last column, each entry's key.hashCode())
+    const int64_t ncols = (s->kind == FWA_SESSION ? 4 : 3) + s->naggs + s->nh + (s->key_kind == FWA_KEY_PREHASHED ? 1 : 0);
     if (bytes != (kHdr + s->maxp + 1 + s->n * ncols) * 8) return false;
     s->koff = w + kHdr;
     s->col = w + kHdr + s->maxp + 1;
@@ -92,6 +113,65 @@ uint64_t field_to_acc(int64_t kind, uint64_t f) {
     return (f & 0x8000000000000000ull) ? ~f : (f | 0x8000000000000000ull);
 }
 
+// DataStream reductions: the width of a reduced field (engine.hip type_size), and a session reduction's accumulator word
+// <-> the field's bits (reduce.inc red_write / ingest.inc acc_input: Integer sums sign-extended, Float values kept as
+// double, MIN / MAX / MINBY / MAXBY as Java-compareTo ordered keys with every NaN the canonical one). TUMBLE entries of
+// FWASNAP1 hold the field itself.
+int red_width(int64_t kind) {
+    switch (kind) {
+        case FWA_SUM_F32: case FWA_MIN_F32: case FWA_MAX_F32: case FWA_SUM_I32: case FWA_MIN_I32: case FWA_MAX_I32:
+        case FWA_FIRST_32: case FWA_SEL_32: case FWA_MINBY_I32: case FWA_MAXBY_I32: case FWA_MINBY_F32: case FWA_MAXBY_F32:
+            return 4;
+        default: return 8;
+    }
+}
+uint64_t f32_of_f64_bits(uint64_t d) { double x; memcpy(&x, &d, 8); const float f = (float)x; uint32_t u; memcpy(&u, &f, 4); return u; }
+uint64_t f64_of_f32_bits(uint64_t u) {
+    const uint32_t w = (uint32_t)u; float f; memcpy(&f, &w, 4);
+    const double x = (double)f; uint64_t d; memcpy(&d, &x, 8);
+    return x != x ? 0x7ff8000000000000ull : d;
+}
+uint64_t red_acc_to_field(int64_t kind, uint64_t a) {
+    switch (kind) {
+        case FWA_SUM_I32: return a & 0xffffffffull;
+        case FWA_SUM_F32: return f32_of_f64_bits(a);
+        case FWA_SUM_I64: case FWA_SUM_F64: return a;
+        case FWA_MIN_I32: case FWA_MAX_I32: case FWA_MINBY_I32: case FWA_MAXBY_I32: return (uint64_t)jm::unord_i64(a) & 0xffffffffull;
+        case FWA_MIN_I64: case FWA_MAX_I64: case FWA_MINBY_I64: case FWA_MAXBY_I64: return (uint64_t)jm::unord_i64(a);
+        case FWA_MIN_F32: case FWA_MAX_F32: case FWA_MINBY_F32: case FWA_MAXBY_F32: return f32_of_f64_bits(jm::unord_bits64(a));
+        default: return jm::unord_bits64(a);                               // MIN / MAX / MINBY / MAXBY_F64
+    }
+}
+uint64_t red_field_to_acc(int64_t kind, uint64_t f) {
+    switch (kind) {
+        case FWA_SUM_I32: return (uint64_t)(int64_t)(int32_t)(uint32_t)f;
+        case FWA_SUM_F32: { const uint32_t w = (uint32_t)f; float x; memcpy(&x, &w, 4); const double d = (double)x; uint64_t b; memcpy(&b, &d, 8); return b; }
+        case FWA_SUM_I64: case FWA_SUM_F64: return f;
+        case FWA_MIN_I32: case FWA_MAX_I32: case FWA_MINBY_I32: case FWA_MAXBY_I32: return jm::ord_i64((int64_t)(int32_t)(uint32_t)f);
+        case FWA_MIN_I64: case FWA_MAX_I64: case FWA_MINBY_I64: case FWA_MAXBY_I64: return jm::ord_i64((int64_t)f);
+        case FWA_MIN_F32: case FWA_MAX_F32: case FWA_MINBY_F32: case FWA_MAXBY_F32: return jm::ord_bits64(f64_of_f32_bits(f));
+        default: {
+            double x; memcpy(&x, &f, 8);
+            return jm::ord_bits64(x != x ? 0x7ff8000000000000ull : f);
+        }
+    }
+}
+
+// java.lang.String keys in the canonical char-byte form (a UTF-16 code unit as 1..3 bytes, 7-bit groups low group first,
+// the last byte below 0x80 and, of a multi-byte unit, not 0). The count of code units; String.hashCode() (h = 31 * h +
+// unit, int wrap -- wire.hip fwa_jstring_hash over the same bytes); one unit's canonical form at p[0 .. n).
+int64_t jstr_units(const std::string& t) { int64_t n = 0; for (unsigned char c : t) n += c < 0x80; return n; }
+int32_t jstr_hash(const std::string& t) {
+    uint32_t h = 0, ch = 0;
+    int sh = 0;
+    for (unsigned char c : t) {
+        ch |= (uint32_t)(c & 0x7f) << sh;
+        sh += 7;
+        if (c < 0x80) { h = 31u * h + (ch & 0xffffu); ch = 0; sh = 0; }
+    }
+    return (int32_t)h;
+}
+
 struct Out {
     std::vector<uint8_t> b;
     void u8(uint8_t v) { b.push_back(v); }
@@ -99,6 +179,13 @@ struct Out {
     void i32(int64_t v) { for (int s = 24; s >= 0; s -= 8) u8((uint8_t)((uint64_t)v >> s)); }
     void i64(uint64_t v) { for (int s = 56; s >= 0; s -= 8) u8((uint8_t)(v >> s)); }
     void le64(uint64_t v) { for (int s = 0; s < 64; s += 8) u8((uint8_t)(v >> s)); }
+    // StringSerializer of a String given as its canonical char bytes: varint(len + 1), then the bytes as they stand
+    void jstr(const std::string& t) {
+        uint64_t n = (uint64_t)jstr_units(t) + 1;
+        while (n >= 0x80) { u8((uint8_t)(n | 0x80)); n >>= 7; }
+        u8((uint8_t)n);
+        b.insert(b.end(), t.begin(), t.end());
+    }
     // BinaryRowData with `arity` 8-byte fixed-length fields, RowKind INSERT (BinaryRowDataSerializer; BinaryRowData
     // layout: header byte then one null bit per field from bit 8 on, 8-byte aligned, BinaryRowData.java:68-123)
     void row(const uint64_t* f, int arity, const bool* isnull = nullptr) {
@@ -211,6 +298,30 @@ struct In {
     }
     int64_t i32() { return (int32_t)get(4); }
     int64_t i64() { return (int64_t)get(8); }
+    // StringSerializer (the inverse of Out::jstr): the char bytes of a non-null String in canonical coding
+    void jstr(std::string* t) {
+        t->clear();
+        uint64_t n = 0;
+        for (int sh = 0;; sh += 7) {
+            const uint64_t c = get(1);
+            if (!ok || sh > 28) { ok = false; return; }
+            n |= (c & 0x7f) << sh;
+            if (c < 0x80) break;
+        }
+        if (n == 0 || (int64_t)(n - 1) > this->n - at) { ok = false; return; }   // null, or more units than bytes left
+        for (uint64_t u = 0; u + 1 < n; ++u) {
+            uint32_t ch = 0;
+            for (int k = 0;; ++k) {
+                const uint64_t c = get(1);
+                if (!ok || k > 2) { ok = false; return; }
+                t->push_back((char)(uint8_t)c);
+                ch |= (uint32_t)(c & 0x7f) << (7 * k);
+                if (c < 0x80) { if (k > 0 && c == 0) ok = false; break; }
+            }
+            if (ch > 0xffffu) ok = false;
+            if (!ok) return;
+        }
+    }
     void row(uint64_t* f, int arity, bool* isnull = nullptr) {
         const int nb = ((arity + 63 + 8) / 64) * 8;
         if (i32() != nb + 8 * arity) { ok = false; return; }
@@ -284,31 +395,56 @@ bool folds_f32(const fwa_config& c) {
     for (int j = 0; j < c.num_aggs; ++j) if (c.aggs[j].kind == FWA_SUM_F32) return true;
     return false;
 }
-bool supported(const fwa_config& c, bool dict = false) {
-    if (c.key_kind == FWA_KEY_PREHASHED) return false;
-    if (c.flags & FWA_CFG_REDUCE) return false;                        // a reduction keeps the reduced element
-    if (folds_f32(c)) return false;                                    // the Float sum buffer is not written
+const char* kUnsupported = "heap layout: DataStream TUMBLE / SLIDE / SESSION aggregates, TUMBLE / SESSION reductions and Table "
+                           "TUMBLE / HOP / CUMULATE / SESSION with a computable key hash";
+const char* kNoKeyPos = "heap layout of a DataStream reduction: set FWA_OPT_HEAP_KEY_POS, the key's position in the reduced "
+                        "tuple (the engine cannot know it)";
+const char* kNoSlideReduce = "heap layout of a SLIDE reduction: the reference keeps one reduced element per window, the engine "
+                             "one per slice, and without the arrival ranks a window's first or selected element cannot be "
+                             "placed in a slice; fwa_snapshot / fwa_restore carry it";
+const char* kNoPlainPrehashed = "heap layout of PREHASHED keys without a key dictionary: their Java serialization is the "
+                                "caller's (String keys: fwa_snapshot_heap_keys with their one-field STRING dictionary)";
+const char* kNoTablePrehashed = "heap layout of PREHASHED keys under Table semantics: their Java serialization is the caller's";
+const char* kNotStringDict = "heap layout of a DataStream handle with a key dictionary: exactly one STRING field (the char bytes "
+                             "of java.lang.String keys); other Java key types stay on fwa_snapshot / fwa_restore";
+const char* kDictLongKeys = "heap layout: a key dictionary beside a handle whose keys are not dictionary ids";
+// nullptr when the heap layout of the handle is written / read, else the reason. dict: a key dictionary was passed, with
+// darity fields of dtypes; key_pos: FWA_OPT_HEAP_KEY_POS.
+const char* refusal(const fwa_config& c, bool dict, int darity, const int32_t* dtypes, int64_t key_pos) {
+    if (folds_f32(c)) return kUnsupported;                             // the Float sum buffer is not written
+    const bool red = (c.flags & FWA_CFG_REDUCE) != 0;
     for (int j = 0; j < c.num_aggs; ++j)                               // reduce kinds: the reduced element, no ACC
-        if (c.aggs[j].kind >= FWA_SUM_I32) return false;
-    if ((c.key_kind == FWA_KEY_GROUP_PREFIXED) != dict) return false;   // dictionary ids <=> a key dictionary
-    if (dict && c.semantics != FWA_SEM_TABLE) return false;            // BinaryRowData keys: Table only
+        if (!red && c.aggs[j].kind >= FWA_SUM_I32) return kUnsupported;
+    if (red) {
+        if (c.semantics != FWA_SEM_DATASTREAM) return kUnsupported;
+        if (c.window_kind == FWA_SLIDE) return kNoSlideReduce;
+        if (c.window_kind != FWA_TUMBLE && c.window_kind != FWA_SESSION) return kUnsupported;
+        if (key_pos < 0 || key_pos > c.num_aggs) return kNoKeyPos;
+    }
+    if (c.key_kind == FWA_KEY_PREHASHED) {                             // String keys: ids of a one-field STRING dictionary
+        if (!dict) return kNoPlainPrehashed;
+        if (c.semantics != FWA_SEM_DATASTREAM) return kNoTablePrehashed;
+        if (darity != 1 || dtypes[0] != FWA_KEY_FIELD_STRING) return kNotStringDict;
+    } else {
+        if (dict && c.key_kind != FWA_KEY_GROUP_PREFIXED) return kDictLongKeys;
+        if ((c.key_kind == FWA_KEY_GROUP_PREFIXED) != dict) return kUnsupported;   // dictionary ids <=> a key dictionary
+        if (dict && c.semantics != FWA_SEM_TABLE) return kNotStringDict;          // BinaryRowData keys: Table only
+    }
     if (c.semantics == FWA_SEM_DATASTREAM)
-        return c.window_kind == FWA_TUMBLE || c.window_kind == FWA_SESSION || c.window_kind == FWA_SLIDE;
-    return c.window_kind == FWA_TUMBLE || c.window_kind == FWA_SLIDE || c.window_kind == FWA_CUMULATE ||
-           c.window_kind == FWA_SESSION;
+        return (c.window_kind == FWA_TUMBLE || c.window_kind == FWA_SESSION || c.window_kind == FWA_SLIDE) ? nullptr : kUnsupported;
+    return (c.window_kind == FWA_TUMBLE || c.window_kind == FWA_SLIDE || c.window_kind == FWA_CUMULATE ||
+            c.window_kind == FWA_SESSION) ? nullptr : kUnsupported;
 }
-const char* kUnsupported = "heap layout: DataStream TUMBLE / SLIDE / SESSION aggregates and Table TUMBLE / HOP / CUMULATE / "
-                           "SESSION with a computable key hash";
 // COUNT(DISTINCT) handles have their own reason: the reference keeps the distinct values as MapView bytes
 const char* kNoDistinct = "heap layout of COUNT(DISTINCT): the set of values (MapView bytes in the reference) is not "
                           "written; fwa_snapshot / fwa_restore carry it";
 const char* kNoFold = "heap layout under FWA_CFG_F32_FOLD: the Float sum buffer of the arrival-order fold is not "
                       "written; fwa_snapshot / fwa_restore carry it";
-const char* why_unsupported(const fwa_config& c) {
+const char* why_unsupported(const fwa_config& c, const char* why) {
     if (folds_f32(c)) return kNoFold;
     for (int j = 0; j < c.num_aggs; ++j)                               // (FWA_AGG_DISTINCT: SUM / AVG(DISTINCT), same view)
         if (c.aggs[j].kind == FWA_COUNT_DISTINCT || (c.aggs[j].kind & FWA_AGG_DISTINCT)) return kNoDistinct;
-    return kUnsupported;
+    return why;
 }
 
 int64_t gcd64(int64_t a, int64_t b) { while (b) { const int64_t t = a % b; a = b; b = t; } return a; }
@@ -608,12 +744,25 @@ static int snapshot_heap_impl(fwa_engine* e, fwa_keydict* dict, fwa_blob* out, i
     fwa_config c;
     int rc = fwa_get_config(e, &c);
     if (rc) return rc;
-    if (!supported(c, dict != nullptr)) return fwa_set_error(e, FWA_E_UNSUPPORTED, why_unsupported(c));
+    int64_t key_pos = -1;
+    if ((rc = fwa_get_option(e, FWA_OPT_HEAP_KEY_POS, &key_pos))) return rc;
     DictRows dr;
     if (dict && (rc = fwa_keydict_host_rows(dict, &dr.arity, dr.types, &dr.slots, &dr.nulls)))
         return fwa_set_error(e, rc, "key dictionary rows");
+    if (const char* why = refusal(c, dict != nullptr, dr.arity, dr.types, key_pos))
+        return fwa_set_error(e, FWA_E_UNSUPPORTED, why_unsupported(c, why));
     for (int i = 0; i < dr.arity; ++i) dr.has_str |= dr.types[i] == FWA_KEY_FIELD_STRING;
     if (dr.has_str && (rc = fwa_keydict_host_strings(dict, &dr.strs))) return fwa_set_error(e, rc, "key dictionary strings");
+    const bool red = (c.flags & FWA_CFG_REDUCE) != 0;
+    const bool skeys = c.key_kind == FWA_KEY_PREHASHED;                // java.lang.String keys: ids of a one-STRING dictionary
+    // a DataStream key: LongSerializer, or StringSerializer of the dictionary's char bytes of an id
+    auto ds_key = [&](Out& o, int64_t key) -> bool {
+        if (!skeys) { o.i64((uint64_t)key); return true; }
+        const uint64_t seq = (uint64_t)key & ((1ull << 48) - 1);
+        if (seq >= dr.nulls.size() || (dr.nulls[seq] & 1)) return false;
+        o.jstr(dr.strs[seq]);
+        return true;
+    };
     // the key as a BinaryRowData: one BIGINT field, or the dictionary row of an id
     auto key_row = [&](Out& o, int64_t key) -> bool {
         if (!dict) { const uint64_t kf = (uint64_t)key; o.row(&kf, 1); return true; }
@@ -640,7 +789,15 @@ static int snapshot_heap_impl(fwa_engine* e, fwa_keydict* dict, fwa_blob* out, i
     const Ids id = ids_of(c);
     FwaDecView dv;
     AccMap am;
-    if ((rc = fwa_dec_view(e, &dv)) || !acc_map(c, dv, &am) || am.ina != (int)s.naggs || am.inh != (int)s.nh) {
+    if (red) {                                   // the reduced fields in order, then the hidden selection columns (not written)
+        am.ic = c;
+        am.na = am.ina = c.num_aggs;
+        am.nh = 0;
+        am.inh = (int)s.nh;
+        for (int j = 0; j < am.na; ++j) { am.hid[j] = -1; am.uw[j] = 1 + j; am.npc[j] = 0; }
+    }
+    if ((!red && ((rc = fwa_dec_view(e, &dv)) || !acc_map(c, dv, &am))) || am.ina != (int)s.naggs || am.inh != (int)s.nh ||
+        (s.key_kind == FWA_KEY_PREHASHED) != skeys) {
         fwa_blob_free(&snap);
         return fwa_set_error(e, FWA_E_STATE, "heap layout: accumulator words do not match the configuration");
     }
@@ -742,9 +899,22 @@ static int snapshot_heap_impl(fwa_engine* e, fwa_keydict* dict, fwa_blob* out, i
                     decb[1 + j] = dec_bytes(T);
                 }
                 for (int h = 0; h < nh; ++h) { f[1 + na + h] = r.w[am.hw[h]]; fnull[1 + na + h] = 0; }
-                if (ds) {
+                if (red) {
+                    // ReducingState: the reduced tuple, the key at its declared position (TupleSerializer). TUMBLE cells
+                    // hold the fields, a session's words its accumulator
+                    o.i64((uint64_t)start); o.i64((uint64_t)end);
+                    keys_ok = ds_key(o, key) && keys_ok;
+                    for (int p = 0; p <= na; ++p) {
+                        if (p == (int)key_pos) { keys_ok = ds_key(o, key) && keys_ok; continue; }
+                        const int j = p < (int)key_pos ? p : p - 1;
+                        const int64_t kind = c.aggs[j].kind;
+                        const uint64_t v = sess ? red_acc_to_field(kind, r.w[1 + j]) : r.w[1 + j];
+                        if (red_width(kind) == 4) o.i32((int64_t)(v & 0xffffffffull));
+                        else o.i64(v);
+                    }
+                } else if (ds) {
                     o.i64((uint64_t)start); o.i64((uint64_t)end);          // TimeWindow.Serializer
-                    o.i64((uint64_t)key);                                  // LongSerializer
+                    keys_ok = ds_key(o, key) && keys_ok;                   // LongSerializer / StringSerializer
                     for (int k = 0; k < arity; ++k) o.i64(f[k]);           // TupleSerializer of the ACC fields
                 } else {
                     if (sess) { o.i64((uint64_t)start); o.i64((uint64_t)end); }   // TR TimeWindow.Serializer :169-172
@@ -763,7 +933,7 @@ static int snapshot_heap_impl(fwa_engine* e, fwa_keydict* dict, fwa_blob* out, i
             o.i32((int64_t)by_key.size());
             for (auto& kv : by_key) {
                 o.u8(0);                                               // VoidNamespaceSerializer: one byte
-                if (ds) o.i64((uint64_t)kv.first);
+                if (ds) keys_ok = ds_key(o, kv.first) && keys_ok;
                 else keys_ok = key_row(o, kv.first) && keys_ok;
                 o.i32((int64_t)kv.second.size());                      // ListSerializer / MapSerializer: size, then
                 for (int64_t i : kv.second) {                          // (actual, state) TimeWindow pairs
@@ -807,7 +977,7 @@ static int snapshot_heap_impl(fwa_engine* e, fwa_keydict* dict, fwa_blob* out, i
         for (const auto& t : timers) {
             o.i64((uint64_t)std::get<0>(t) ^ 0x8000000000000000ull);   // MathUtils.flipSignBit
             const int64_t key = std::get<1>(t);
-            if (ds) { o.i64((uint64_t)key); o.i64((uint64_t)std::get<2>(t)); o.i64((uint64_t)std::get<3>(t)); }
+            if (ds) { keys_ok = ds_key(o, key) && keys_ok; o.i64((uint64_t)std::get<2>(t)); o.i64((uint64_t)std::get<3>(t)); }
             else {
                 keys_ok = key_row(o, key) && keys_ok;
                 if (sess) o.i64((uint64_t)std::get<2>(t));             // TimeWindow namespace
@@ -831,7 +1001,8 @@ static int restore_heap_impl(fwa_engine* e, fwa_keydict* dict, const void* const
     fwa_config c;
     int rc = fwa_get_config(e, &c);
     if (rc) return rc;
-    if (!supported(c, dict != nullptr)) return fwa_set_error(e, FWA_E_UNSUPPORTED, why_unsupported(c));
+    int64_t key_pos = -1;
+    if ((rc = fwa_get_option(e, FWA_OPT_HEAP_KEY_POS, &key_pos))) return rc;
     int32_t darity = 1;
     int32_t dtypes[FWA_KEYDICT_MAX_ARITY] = {};
     bool dstr = false;
@@ -840,21 +1011,41 @@ static int restore_heap_impl(fwa_engine* e, fwa_keydict* dict, const void* const
         if ((rc = fwa_keydict_host_rows(dict, &darity, dtypes, &tmp_s, &tmp_n))) return fwa_set_error(e, rc, "key dictionary");
         for (int i = 0; i < darity; ++i) dstr |= dtypes[i] == FWA_KEY_FIELD_STRING;
     }
+    if (const char* why = refusal(c, dict != nullptr, dict ? darity : 0, dtypes, key_pos))
+        return fwa_set_error(e, FWA_E_UNSUPPORTED, why_unsupported(c, why));
+    const bool red = (c.flags & FWA_CFG_REDUCE) != 0;
+    const bool skeys = c.key_kind == FWA_KEY_PREHASHED;                // java.lang.String keys (see snapshot_heap_impl)
     const bool ds = c.semantics == FWA_SEM_DATASTREAM;
     const bool sess = c.window_kind == FWA_SESSION;
     const bool ds_slide = ds && c.window_kind == FWA_SLIDE;
     const Ids id = ids_of(c);
     FwaDecView dv;
     AccMap am;
-    if ((rc = fwa_dec_view(e, &dv)) || !acc_map(c, dv, &am))
+    if (red) {
+        // the reduced fields in order; the hidden selection columns of the FWASNAP1 entries (header word 25) as the
+        // fresh handle itself numbers them
+        fwa_blob fresh{nullptr, 0};
+        Snap fs;
+        if ((rc = fwa_snapshot(e, &fresh))) return rc;
+        const bool okp = parse(fresh.data, fresh.size, &fs);
+        fwa_blob_free(&fresh);
+        if (!okp || fs.n != 0) return fwa_set_error(e, FWA_E_STATE, "restore needs a fresh handle");
+        am.ic = c;
+        am.na = am.ina = c.num_aggs;
+        am.nh = 0;
+        am.inh = (int)fs.nh;
+        for (int j = 0; j < am.na; ++j) { am.hid[j] = -1; am.uw[j] = 1 + j; am.npc[j] = 0; }
+    } else if ((rc = fwa_dec_view(e, &dv)) || !acc_map(c, dv, &am)) {
         return fwa_set_error(e, FWA_E_STATE, "heap layout: accumulator words do not match the configuration");
+    }
     const int na = am.na, nh = am.nh, ina = am.ina, inh = am.inh, arity = 1 + na + nh, maxp = c.max_parallelism;
     const fwa_config& ic = am.ic;
     bool isdec[1 + FWA_MAX_AGGS + FWA_MAX_COLS] = {};
     for (int j = 0; j < na; ++j) isdec[1 + j] = am.npc[j] != 0;
     const int64_t g = ds ? c.size_ms : slice_width(c);
-    const int64_t ncols = (sess ? 4 : 3) + ina + inh;
+    const int64_t ncols = (sess ? 4 : 3) + ina + inh + (skeys ? 1 : 0);   // (String keys: the hash column, filled last)
     bool dec_range = true;
+    int64_t red_rank = 0;                                    // reductions: the running index of the state entries
     std::vector<std::vector<int64_t>> blobs((size_t)n_bodies);
     std::vector<const void*> ptrs;
     std::vector<int64_t> bsz;
@@ -894,6 +1085,23 @@ static int restore_heap_impl(fwa_engine* e, fwa_keydict* dict, const void* const
         std::map<std::string, int64_t> comp_raw;                     // rows with STRING fields: by their bytes
         std::vector<uint64_t> comp_slots, comp_nulls;
         std::vector<std::string> comp_strs;
+        std::vector<int32_t> comp_hash;                              // String keys: String.hashCode() per placeholder
+        // a DataStream key: a Long, or a String -> its placeholder
+        auto ds_read_key = [&](In& in) -> int64_t {
+            if (!skeys) return in.i64();
+            std::string t;
+            in.jstr(&t);
+            if (!in.ok) return 0;
+            auto it = comp_raw.find(t);
+            if (it != comp_raw.end()) return it->second;
+            const int64_t idx = (int64_t)comp_nulls.size();
+            comp_raw.emplace(t, idx);
+            comp_slots.push_back(0);
+            comp_nulls.push_back(0);
+            comp_hash.push_back(jstr_hash(t));
+            comp_strs.push_back(std::move(t));
+            return idx;
+        };
         auto read_key = [&](In& in) -> int64_t {
             if (!dict) { uint64_t kf; in.row(&kf, 1); return (int64_t)kf; }
             if (dstr) {
@@ -935,14 +1143,14 @@ static int restore_heap_impl(fwa_engine* e, fwa_keydict* dict, const void* const
                 for (int64_t i = 0; i < cnt && in.ok; ++i) {
                     if (sid == id.proc || sid == id.event) {           // timers: re-derived from the window state
                         in.i64();
-                        if (ds) { in.i64(); in.i64(); in.i64(); }
+                        if (ds) { ds_read_key(in); in.i64(); in.i64(); }
                         else { read_key(in); in.i64(); if (sess) in.i64(); }
                         continue;
                     }
                     if (sid == id.mset) {                              // merging-window-set: (actual, state) pairs
                         in.get(1);                                     // MergingWindowSet(...) :83-87
                         int64_t key;
-                        if (ds) key = in.i64();
+                        if (ds) key = ds_read_key(in);
                         else key = read_key(in);
                         const int64_t m = in.i32();
                         for (int64_t q = 0; q < m && in.ok; ++q) {
@@ -955,7 +1163,39 @@ static int restore_heap_impl(fwa_engine* e, fwa_keydict* dict, const void* const
                     }
                     int64_t key, start, end;
                     for (int k = 0; k < arity; ++k) fnull[k] = false;
-                    if (ds) { start = in.i64(); end = in.i64(); key = in.i64(); for (int k = 0; k < arity; ++k) f[k] = (uint64_t)in.i64(); }
+                    if (red) {
+                        // the reduced tuple: the key again at its position, the fields at their widths. A TUMBLE entry's
+                        // cells are the fields (a 4-byte one zero-extended) and its count column and hidden selection
+                        // columns the running index; a session's word is its accumulator and its COUNT(*) 1 (the
+                        // ReducingState holds one element; no output reads the count)
+                        start = in.i64(); end = in.i64(); key = ds_read_key(in);
+                        uint64_t cell[FWA_MAX_AGGS] = {};
+                        for (int p = 0; p <= na && in.ok; ++p) {
+                            if (p == (int)key_pos) { if (ds_read_key(in) != key) in.ok = false; continue; }
+                            const int j = p < (int)key_pos ? p : p - 1;
+                            cell[j] = in.get(red_width(c.aggs[j].kind));
+                        }
+                        if (!in.ok) break;
+                        if (sess) {
+                            Pending p{kg, key, start, end, {}};
+                            p.w.push_back(1);
+                            p.w.push_back((int64_t)red_field_to_acc(c.aggs[0].kind, cell[0]));
+                            for (int h = 0; h < inh; ++h) p.w.push_back(0);
+                            pend.push_back(std::move(p));
+                            continue;
+                        }
+                        std::vector<int64_t>& v = per[(size_t)kg];
+                        v.push_back(key);
+                        v.push_back(start);
+                        v.push_back(red_rank);
+                        for (int j = 0; j < na; ++j) v.push_back((int64_t)cell[j]);
+                        for (int h = 0; h < inh; ++h) v.push_back(red_rank);
+                        if (skeys) v.push_back(0);
+                        ++red_rank;
+                        ++total;
+                        continue;
+                    }
+                    if (ds) { start = in.i64(); end = in.i64(); key = ds_read_key(in); for (int k = 0; k < arity; ++k) f[k] = (uint64_t)in.i64(); }
                     else {
                         start = sess ? in.i64() : 0;                   // Table sessions: TimeWindow namespace
                         end = in.i64();
@@ -980,6 +1220,7 @@ static int restore_heap_impl(fwa_engine* e, fwa_keydict* dict, const void* const
                     v.push_back(key);
                     v.push_back(start);
                     words(v);
+                    if (skeys) v.push_back(0);
                     ++total;
                 }
             }
@@ -994,6 +1235,7 @@ static int restore_heap_impl(fwa_engine* e, fwa_keydict* dict, const void* const
                 v.push_back(st);
                 v.insert(v.end(), p.w.begin(), p.w.end());
                 v.push_back(en);
+                if (skeys) v.push_back(0);
                 ++total;
             }
             pend.clear();
@@ -1005,6 +1247,7 @@ static int restore_heap_impl(fwa_engine* e, fwa_keydict* dict, const void* const
                     v.push_back(kw.first);
                     v.push_back(sl.first);
                     for (uint64_t x : sl.second) v.push_back((int64_t)x);
+                    if (skeys) v.push_back(0);
                     ++total;
                 }
             }
@@ -1013,7 +1256,22 @@ static int restore_heap_impl(fwa_engine* e, fwa_keydict* dict, const void* const
         if (!in.ok) return fwa_set_error(e, FWA_E_ARG, "heap body: truncated or malformed");
         if (!dec_range)
             return fwa_set_error(e, FWA_E_UNSUPPORTED, "heap body: a DECIMAL sum of a DECIMAL(p <= 18) column past 2^95");
-        if (dict && !comp_nulls.empty()) {                            // placeholder keys -> dictionary ids
+        if (skeys && !comp_nulls.empty()) {                           // String placeholders -> dictionary ids, hash column
+            std::vector<int64_t> ids(comp_nulls.size());
+            if ((rc = fwa_keydict_encode_host_str(dict, comp_slots.data(), comp_nulls.data(), comp_strs, (int64_t)ids.size(),
+                                                  ids.data())))
+                return fwa_set_error(e, rc, "key dictionary encode");
+            for (int kg = 0; kg < maxp; ++kg) {
+                std::vector<int64_t>& v = per[(size_t)kg];
+                for (size_t r = 0; r < v.size(); r += (size_t)ncols) {
+                    const int32_t h = comp_hash[(size_t)v[r]];
+                    if (jm::key_group_of(0, FWA_KEY_PREHASHED, h, maxp) != kg)
+                        return fwa_set_error(e, FWA_E_ARG, "heap body: a String key outside its key group (maxParallelism?)");
+                    v[r + (size_t)ncols - 1] = h;
+                    v[r] = ids[(size_t)v[r]];
+                }
+            }
+        } else if (dict && !comp_nulls.empty()) {                     // placeholder keys -> dictionary ids
             std::vector<int64_t> ids(comp_nulls.size());
             rc = dstr ? fwa_keydict_encode_host_str(dict, comp_slots.data(), comp_nulls.data(), comp_strs, (int64_t)ids.size(),
                                                     ids.data())

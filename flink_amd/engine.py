@@ -156,7 +156,7 @@ OPTIONS = {"skew_merge": 1, "window_passes": 2, "narrow_entries": 3, "session_ce
            "stragglers": 21, "key_table_digest": 22, "distinct_index_us": 23, "distinct_count_us": 24,
            "distinct_count_steps": 25, "stale_retires": 26, "f32_fold_slots": 27, "f32_fold_rebuilds": 28,
            "f32_fold_resolve_us": 29, "f32_fold_sort_us": 30, "f32_fold_runs_us": 31, "f32_fold_rows_us": 32,
-           "fast_slice_pushes": 33, "key_table_shape": 34}
+           "fast_slice_pushes": 33, "key_table_shape": 34, "heap_key_pos": 35}
 # options applied to every new handle of this process before its own (test tooling sets these, e.g.
 # tests/forced_modes_check.py); empty in production
 DEFAULT_OPTIONS = {}
@@ -434,7 +434,9 @@ class WindowAggregator:
     def snapshot_heap(self, keydict=None):
         """Keyed window state in Flink's heap-backend key-group byte layout (fwa_snapshot_heap): returns
         (body bytes, per-key-group section offsets, watermark). keydict: the flink_amd.keydict.KeyDictionary of an
-        engine on dictionary ids (key rows written as its multi-column BinaryRowData rows)."""
+        engine on dictionary ids (key rows written as its multi-column BinaryRowData rows; on a DataStream
+        KEY_PREHASHED handle a one-field STRING dictionary of java.lang.String keys, written by StringSerializer's
+        rule). A reduce handle needs set_option("heap_key_pos", p): the key's position in the reduced tuple."""
         b = Blob()
         nkg = self.cfg.kg_end - self.cfg.kg_start + 1
         offs = np.zeros(nkg, np.int64)

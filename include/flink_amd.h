@@ -196,7 +196,9 @@ enum fwa_agg_kind {
  * order-free, float sums aside), with any allowed lateness
  * (late firings emit the reduced element after each late element, in arrival order); every aggregate is a field
  * of the reduced tuple: at most one MINBY / MAXBY, FWA_SEL_* only with it and FWA_FIRST_* only without it, SUM / MIN /
- * MAX over any type; COUNT, AVG, DECIMAL, NULLs, record lists, partials and the heap layout are FWA_E_UNSUPPORTED.
+ * MAX over any type; COUNT, AVG, DECIMAL, NULLs, record lists and partials are FWA_E_UNSUPPORTED. The heap layout
+ * (fwa_snapshot_heap*, below) is written for TUMBLE and SESSION reductions once FWA_OPT_HEAP_KEY_POS says where the key
+ * sits in the reduced tuple; without it, and for SLIDE reductions, it is FWA_E_UNSUPPORTED.
  * fwa_snapshot / fwa_restore work: an entry per (key, slice) holds the slice's reduced fields (acc_j: the field value,
  * a 4-byte field zero-extended) and, in its count column, the arrival rank of the element it selected; a restore
  * (any key-group split) pushes the entries back as elements in that order, so later windows equal an uninterrupted
@@ -622,9 +624,24 @@ int fwa_restore(fwa_engine* e, const void* const* blobs, const int64_t* sizes, i
  *     flink_amd/csrc/heap_snapshot.cpp describes.
  * kg_offsets[g - kg_start] receives the byte offset of key group g's section (KeyGroupRangeOffsets; the Java shim
  * writes its KeyedBackendSerializationProxy header in front and shifts them), *watermark the operator watermark
- * (union list state, SlicingWindowOperator.java:204-209). PREHASHED keys (their Java serialization is the caller's)
- * and DataStream reductions (FWA_CFG_REDUCE): FWA_E_UNSUPPORTED -- fwa_snapshot / fwa_restore carry both, PREHASHED
- * keys with their hashes (dense and session handles). The blob is freed with fwa_blob_free. */
+ * (union list state, SlicingWindowOperator.java:204-209).
+ *   DataStream reductions (FWA_CFG_REDUCE; WindowedStream.sum / min / max / minBy / maxBy): the window-contents state
+ *     is a ReducingState whose value is the reduced tuple itself (TupleSerializer: the fields in order, big-endian, no
+ *     null mask) -- the key (as the entry's key is written) at tuple position FWA_OPT_HEAP_KEY_POS, the handle's
+ *     aggregates as the other fields in order: 8 bytes (Long, or Double bits) for *_I64, *_F64, FIRST_64 / SEL_64, 4
+ *     bytes for *_I32, *_F32, FIRST_32 / SEL_32. Accepted: TUMBLE with any allowed lateness (one entry per (key,
+ *     window); a fired window that is not yet cleaned keeps its state and only its cleanup timer) and SESSION over
+ *     Tuple2<key, f1> (the session layout above with that value). State ids and timers as for aggregates. A restore
+ *     pushes every state entry back as one element, in the order of the bodies: a ReducingState holds one element and
+ *     every later element folds after it, so first-element and tie rules (FWA_CFG_BY_LAST included) continue as in the
+ *     reference. FWA_E_UNSUPPORTED: a handle whose FWA_OPT_HEAP_KEY_POS is not set (the engine cannot know where the
+ *     key sits; fwa_last_error names the option); SLIDE reductions (the reference keeps one reduced element per
+ *     window and the engine one per slice: without the arrival ranks a window's first or selected element cannot be
+ *     placed in a slice); handles with FWA_CFG_F32_FOLD (the Float sum buffer is not written).
+ *   FWA_KEY_PREHASHED handles: FWA_E_UNSUPPORTED here -- their keys' Java serialization is the caller's -- except
+ *     String keys through fwa_snapshot_heap_keys (below). fwa_snapshot / fwa_restore carry every refused case, PREHASHED
+ *     keys with their hashes (dense and session handles).
+ * The blob is freed with fwa_blob_free. */
 int fwa_snapshot_heap(fwa_engine* e, fwa_blob* out, int64_t* kg_offsets, int64_t* watermark);
 
 /* Restore a fresh handle from heap-layout bodies (as written by fwa_snapshot_heap on handles with the same window
@@ -717,11 +734,16 @@ enum fwa_option {
                                          numbers with its 32-bit division: no shift time zone, slice size * 4096 below
                                          2^32 ms and the first live slice number inside +-2^40; every other two-phase
                                          push takes the exact 64-bit floor division (fwa_get_option) */
-    FWA_OPT_KEY_TABLE_SHAPE = 34      /* read only: the key table's segmentation, seg_log | part_bits << 8 -- the table
+    FWA_OPT_KEY_TABLE_SHAPE = 34,     /* read only: the key table's segmentation, seg_log | part_bits << 8 -- the table
                                          is 2^part_bits segments of 2^seg_log slots; mix64(key)'s top part_bits pick the
                                          segment, its low seg_log bits (rounded down to an 8-slot bucket) the home slot
                                          inside it (fwa_get_option; diagnostic: tests aim key sets with it). Handles
                                          that keep record lists have no key table: FWA_E_UNSUPPORTED */
+    FWA_OPT_HEAP_KEY_POS = 35         /* FWA_CFG_REDUCE handles: the position of the key field in the reduced tuple,
+                                         0 .. num_aggs (the handle's aggregates are the other fields in order) -- the one
+                                         thing fwa_snapshot_heap / fwa_restore_heap need of a reduction that the
+                                         aggregate list does not say. Default -1: not declared, and the heap layout of
+                                         the handle stays FWA_E_UNSUPPORTED. A value outside the range: FWA_E_ARG */
 };
 int fwa_set_option(fwa_engine* e, int32_t option, int64_t value);
 /* The option's effective value: for the tri-state options 1 if the handle currently takes that path (forced, or
@@ -789,8 +811,25 @@ int fwa_keydict_encode(fwa_keydict* d, const void* const* cols, const uint8_t* c
                        int32_t* hashes);
 /* Device pointers: the key columns (and NULL flags, if nulls != NULL) of n ids from this dictionary. */
 int fwa_keydict_decode(fwa_keydict* d, const int64_t* ids, int64_t n, void* const* cols, uint8_t* const* nulls);
-/* fwa_snapshot_heap / fwa_restore_heap for an engine on dictionary ids (Table semantics): key rows are written and
- * read as the dictionary's BinaryRowData rows of `arity` fields (restored rows are encoded into `dict`). */
+/* fwa_snapshot_heap / fwa_restore_heap for an engine on dictionary ids.
+ * Table semantics (FWA_KEY_GROUP_PREFIXED): key rows are written and read as the dictionary's BinaryRowData rows of
+ * `arity` fields (restored rows are encoded into `dict`).
+ * DataStream semantics with FWA_KEY_PREHASHED: java.lang.String keys. `dict` has exactly one field, an
+ * FWA_KEY_FIELD_STRING whose values are the canonical char bytes of the Strings (every UTF-16 code unit as 1..3 bytes
+ * of 7-bit groups, low group first -- what StringSerializer writes behind the length and what fwa_jstring_hash hashes),
+ * and the handle was pushed the ids beside String.hashCode(). A key is written as StringSerializer writes it:
+ * varint(len + 1), len = the UTF-16 code units = the stored bytes with bit 7 clear, then the stored bytes as they
+ * stand. The key group of an entry is assignToKeyGroup(hash) of the hash the engine kept for its key, never bits 48-63
+ * of the id (the BinaryRowData hash's group, which means nothing here). A restore parses each key (the null string 00,
+ * a non-canonical char coding or a length past the section: FWA_E_ARG, as for any malformed body), encodes the distinct
+ * keys into `dict`, computes String.hashCode() over the code units (h = 31 * h + unit, int wrap: fwa_jstring_hash's
+ * value for the same bytes) and places every entry in its key group with it, under any new key-group split; a key
+ * found in another key group's section is FWA_E_ARG. Accepted: DataStream TUMBLE / SLIDE / SESSION aggregates (the
+ * value is the ACC tuple of fwa_snapshot_heap) and the TUMBLE / SESSION reductions described there.
+ * FWA_E_UNSUPPORTED, with the reason in fwa_last_error: PREHASHED without a dictionary (fwa_snapshot_heap) or under
+ * Table semantics; a dictionary under DataStream semantics that is not exactly one STRING field; a dictionary beside
+ * a JAVA_LONG / BINROW_BIGINT handle. Other Java key types (Integer, tuples, POJOs, BigDecimal) stay on the engine blob
+ * (fwa_snapshot) plus the caller's own (id, serialized key) pairs. */
 int fwa_snapshot_heap_keys(fwa_engine* e, fwa_keydict* dict, fwa_blob* out, int64_t* kg_offsets, int64_t* watermark);
 int fwa_restore_heap_keys(fwa_engine* e, fwa_keydict* dict, const void* const* bodies, const int64_t* sizes,
                           const int64_t* watermarks, int32_t n_bodies);
